@@ -11,6 +11,13 @@ when none set WORLD_SIZE, from bench.py itself: the parent process counts the
 devices (no GPU call), starts N rank processes with the launcher's variables
 and relays rank 0's JSON line (`self_launch`).
 
+A plain run sets up, warms up, times the K steps once (`ms_per_step` = that
+time / K), writes its outputs if `--dump-outputs DIR` is given and prints the
+line.  Everything else the benchmark measures -- the repetitions of the K steps
+and their median, the hipEvent kernel profile and roofline, the flat-copy
+ceiling, the CPU baseline, the clock probe and box state, the N > 1 slab
+parity self-check and per_rank records -- runs only with `--full`.
+
 Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).
 """
 import argparse
@@ -45,10 +52,20 @@ def parse():
     # ambiguous abbreviation of its own options)
     p.add_argument("--n", "--edge", dest="n", type=int, default=512, help="global grid edge (nodes)")
     p.add_argument("--path", default="auto", choices=["auto", "generic", "split", "fused"])
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: --reps repetitions of "
+                        "the K steps (value = their median), kernel profile and roofline, copy "
+                        "ceiling, CPU baseline, clock probe, box state, N > 1 parity and per_rank")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the state the last step left (what "
+                        "Context.download() returns, inner nodes) as DIR/<name>.npy, float64, at "
+                        "most 64 MB: the whole grid when it fits, else 8 fixed seeded boxes")
     p.add_argument("--reps", type=int, default=9,
-                   help="repetitions of the K timed steps; value = median (BASELINE.md asks "
-                        "for at least 5; more keeps the GPU busy for a visible share of the run)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="with --full: repetitions of the K timed steps; value = median (BASELINE.md "
+                        "asks for at least 5; more keeps the GPU busy for a visible share of the "
+                        "run).  A plain run times the K steps once")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=5.0,
                    help="bound on each of the two CPU baseline samples")
     p.add_argument("--rows-per-block", type=int, default=0,
@@ -384,6 +401,59 @@ def multi_gpu_parity(dist, world, rank, device, U, U1, L, channels, gcm_amd):
     return {"ok": res[0], "grid": [Xg, Y, Z], "slabs": world, "steps": 3, "path": path}
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: upper bound on what all ranks write together
+DUMP_BOXES = 8
+
+
+def dump_boxes(sizes, budget, seed=0x5EED):
+    """--dump-outputs sample of a slab too large for `budget` bytes: DUMP_BOXES
+    cubes of inner nodes (local origins, edge).  Box 0 sits in the slab's low
+    corner, box 1 in its high corner, the others where a generator seeded with
+    `seed` puts them -- a function of the slab's sizes alone, so two builds
+    sample the same nodes."""
+    import numpy as np
+    edge = int((budget / (DUMP_BOXES * 9 * 8)) ** (1.0 / 3.0))
+    edge = max(1, min([edge] + list(sizes)))
+    rng = np.random.default_rng(seed)
+    origins = [[0, 0, 0], [s - edge for s in sizes]]
+    while len(origins) < DUMP_BOXES:
+        origins.append([int(rng.integers(0, s - edge + 1)) for s in sizes])
+    return origins, edge
+
+
+def dump_outputs(dirname, ctx, gcm_amd, sizes, start, device, rank, world):
+    """--dump-outputs DIR: the current layer as the last timed step left it (what
+    Context.download() hands a caller), inner nodes only, float64 [.., 9], as
+    DIR/state.npy (N > 1: DIR/state_rank<r>.npy, this rank's slab).  A slab
+    within the byte budget is written whole, [X, Y, Z, 9]; a larger one as
+    dump_boxes' cubes, [8, edge, edge, edge, 9], copied out on the device
+    (gcmx_copy_box into a small context) so the whole layer never crosses to the
+    host.  Returns the line's record of what was written."""
+    import numpy as np
+    bs = 2
+    budget = DUMP_BYTES // world
+    os.makedirs(dirname, exist_ok=True)
+    name = "state" if world == 1 else f"state_rank{rank}"
+    if int(np.prod(sizes)) * 9 * 8 <= budget:
+        inner = tuple(slice(bs, bs + s) for s in sizes)
+        out = ctx.download().reshape(tuple(s + 2 * bs for s in sizes) + (9,))[inner]
+        what = {"sample": "whole slab"}
+    else:
+        origins, edge = dump_boxes(sizes, budget)
+        box = gcm_amd.Context(3, bs, [edge] * 3, start=list(start), device=device)
+        out = np.empty((len(origins), edge, edge, edge, 9))
+        try:
+            for i, o in enumerate(origins):
+                box.copy_box([0, 0, 0], [edge] * 3, ctx, o)
+                out[i] = box.download().reshape((edge + 2 * bs,) * 3 + (9,))[bs:-bs, bs:-bs, bs:-bs]
+        finally:
+            box.close()
+        what = {"sample": f"{len(origins)} boxes of {edge}^3 inner nodes", "origins": origins}
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    np.save(os.path.join(dirname, name + ".npy"), out)
+    return {"file": name + ".npy", "shape": list(out.shape), "dtype": "float64", **what}
+
+
 def emulate_slabs(a):
     """--emulate-slabs K on one GPU: the config-3 decomposition (K X slabs of the
     N^3 grid) as the ranks of an in-process group, so every step runs the exact
@@ -514,8 +584,14 @@ def main():
     U, U1, L = isotropic_elastic_matrices(3, 4.0, 2.0, 1.0)
     tau = 0.9 * 1.0 / 1.0  # Courant * h / max|lambda| (Engine.cpp:124-140)
 
+    # A plain run times the K steps once and measures nothing beside them.
+    reps = max(1, a.reps) if a.full else 1
+    want_box = a.full and not a.no_box_state
+    want_clock = a.full and not a.no_clock_probe
+    want_profile = a.full and not a.no_profile
+
     box = None
-    if not a.no_box_state:  # every rank reads its own GPU's state (per_rank for N > 1)
+    if want_box:  # every rank reads its own GPU's state (per_rank for N > 1)
         try:
             box = box_state.static_state(device)
         except Exception as e:  # reported context, never required
@@ -525,7 +601,7 @@ def main():
     if a.prealloc_gb > 0:  # measurement only: shifts the layers' placement
         hold = torch.empty(int(a.prealloc_gb * (1 << 30)), dtype=torch.uint8, device=f"cuda:{device}")
     ctx = gcm_amd.Context(3, 2, [X, N, N], start=[x0, 0, 0], device=device)
-    placement = layer_placement(ctx)
+    placement = layer_placement(ctx) if a.full else None
     ctx.set_materials(U[None], U1[None], L[None])
     ctx.set_path(paths[a.path])
     if a.rows_per_block:
@@ -542,7 +618,7 @@ def main():
         ctx.comm_init(gcm_amd.unique_id(), 1, 0, 0, 0)
     ctx.sync()
     parity = None
-    if world > 1:
+    if world > 1 and a.full:
         parity = multi_gpu_parity(dist, world, rank, device, U, U1, L, ctx.comm_channels_per_peer, gcm_amd)
         log(f"[rank {rank}] multi-GPU slab parity: {parity}")
     log(f"[rank {rank}] slab x[{x0},{x0 + X}) of {N}^3, {ctx.device_bytes / 1e9:.1f} GB, "
@@ -559,19 +635,19 @@ def main():
     warm_ms = (time.perf_counter() - tw) / max(1, a.warmup) * 1e3
     # one co-resident wave samples the shader clock over the timed repetitions
     clock = None
-    if not a.no_clock_probe:
-        span = min(20.0, max(0.2, 1.15 * a.reps * a.steps * warm_ms * 1e-3 + 0.05))
+    if want_clock:
+        span = min(20.0, max(0.2, 1.15 * reps * a.steps * warm_ms * 1e-3 + 0.05))
         ctx.clock_probe_start(span, max(50.0, span * 1e6 / 4000))
 
-    # K timed steps, repeated `reps` times (median reported).  When profiling,
+    # K timed steps; with --full repeated `reps` times (median reported).  When profiling,
     # every launch in these same repetitions is bracketed by hipEvents on the
     # stream it runs on (gcmx_profile_enable), which is where kernel_avg_ms
     # comes from.
-    if not a.no_profile:
+    if want_profile:
         ctx.profile(True)
         ctx.profile_reset()
     sampler = None
-    if not a.no_box_state:
+    if want_box:
         try:
             sampler = box_state.Sampler(device).start()
         except Exception as e:  # reported context, never required
@@ -579,7 +655,7 @@ def main():
     rep_s = []
     rep_kernels = []  # per repetition: the profile's totals accumulated in that repetition
     prev = {}
-    for _ in range(max(1, a.reps)):
+    for _ in range(reps):
         barrier()
         ctx.sync()
         t0 = time.perf_counter()
@@ -593,23 +669,26 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
         rep_s.append(el)
-        if not a.no_profile:
+        if want_profile:
             cur = ctx.profile_read()
             rep_kernels.append({k: (v["total_ms"] - prev.get(k, {}).get("total_ms", 0.0),
                                     v["launches"] - prev.get(k, {}).get("launches", 0))
                                 for k, v in cur.items()})
             prev = cur
     sampled = sampler.stop() if sampler is not None else None
-    if not a.no_clock_probe:
+    if want_clock:
         clock = clock_summary(ctx.clock_probe_read())
     kernels = {}
-    if not a.no_profile:
+    if want_profile:
         kernels = ctx.profile_read()
         ctx.profile(False)
+    dumped = None
+    if a.dump_outputs:  # the state the last timed step left, before anything else runs
+        dumped = dump_outputs(a.dump_outputs, ctx, gcm_amd, [X, N, N], [x0, 0, 0], device, rank, world)
     el = sorted(rep_s)[len(rep_s) // 2]
     per_rank = None
     if (world > 1 or a.rccl_self) and kernels:
-        rec = rank_record(ctx, rank, kernels, a.steps * max(1, a.reps), el / a.steps * 1e3)
+        rec = rank_record(ctx, rank, kernels, a.steps * reps, el / a.steps * 1e3)
         rec["box"] = box_summary(box, sampled)
         if dist is not None:
             recs = [None] * world if rank == 0 else None
@@ -660,7 +739,7 @@ def main():
             log(f"copy ceiling failed: {e}")
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         try:
             cpu = cpu_baseline(a.cpu_seconds)
         except Exception as e:  # the baseline is reported, never required
@@ -677,6 +756,7 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(el / a.steps * 1e3, 4),
+            "full": a.full,
             "reps": len(rep_s),
             "rep_ms_per_step": [round(r / a.steps * 1e3, 4) for r in rep_s],
             "higher_is_better": True,
@@ -710,10 +790,13 @@ def main():
             "multi_gpu_parity": parity,
             # N > 1 (or --rccl-self): every rank's exchange / compute split (rank_record)
             "per_rank": per_rank,
-            # what distinguishes one process's run from another's on the same box
+            # --dump-outputs: what this rank wrote (dump_outputs)
+            **({"outputs": dumped} if dumped else {}),
+            # --full only: what distinguishes one process's run from another's on the same box
             # (VERDICT r3 item 1): the layers' placement, the clock under load,
             # the allocation order
-            "process_state": {"layers": placement, "clock": clock,
+            "process_state": None if not a.full else
+                             {"layers": placement, "clock": clock,
                               # the box: partition modes, power cap,
                               # firmware, DPM tables (tools/box_state.py), and the DPM
                               # levels / power / temperatures sampled during the reps

@@ -9,7 +9,7 @@ OUT=${1:-gpurun_out/r5/box}
 mkdir -p $OUT
 BOX_ONLY=1 PROBE_REPS=150 timeout -k 10 120 python3 tools/power_probe.py $OUT/box_probe.json -- ./tools/xyz_probe > $OUT/box_probe.txt 2>&1 || { echo "box probe rc=$?"; cat $OUT/box_probe.txt; exit 1; }
 cat $OUT/box_probe.txt
-timeout -k 10 300 python bench.py --steps 100 --reps 7 --no-cpu-baseline > $OUT/bench_long.json 2> $OUT/bench_long.err || { echo "bench rc=$?"; tail -5 $OUT/bench_long.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 100 --full --reps 7 --no-cpu-baseline > $OUT/bench_long.json 2> $OUT/bench_long.err || { echo "bench rc=$?"; tail -5 $OUT/bench_long.err; exit 1; }
 python3 - $OUT/bench_long.json <<'PY'
 import json, statistics, sys
 d = json.load(open(sys.argv[1])); ps = d["process_state"]; b = ps["box"]; s = ps["box_during_reps"] or {}

@@ -21,7 +21,7 @@ for spec in ${LIBS:-base=gcm_amd/lib/libgcmx.so}; do
   for set in "${PASSES[@]}"; do
     k=$((k+1)); mkdir -p $OUT/$name
     GCMX_LIB=$lib timeout -s KILL 90 rocprofv3 --pmc $set --output-format csv -d $OUT/$name/p$k -o run -- \
-      python3 bench.py --n $N --steps 3 --reps 1 --warmup 1 --no-cpu-baseline --no-profile \
+      python3 bench.py --n $N --steps 3 --full --reps 1 --warmup 1 --no-cpu-baseline --no-profile \
       > $OUT/$name/p$k.json 2> $OUT/$name/p$k.err || { echo "$name pass $k failed rc=$?"; tail -3 $OUT/$name/p$k.err; exit 1; }
     echo "$name pass $k ok"
   done

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_${TAG:-r1}
 mkdir -p $OUT
 N=${N:-512}
-BA="--n $N --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline"
+BA="--n $N --steps ${STEPS:-10} --warmup 2 --full --no-cpu-baseline"
 set -o pipefail
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
   python3 bench.py $BA > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "trace failed rc=$?"; exit 1; }
@@ -28,7 +28,7 @@ if [ "${SQ:-0}" = 1 ]; then
              "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE GRBM_COUNT"; do
     i=$((i+1))
     timeout -k 10 120 rocprofv3 --pmc $set --output-format csv -d $OUT/sq$i -o run -- \
-      python3 bench.py --n $N --steps 3 --warmup 1 --no-cpu-baseline --no-profile \
+      python3 bench.py --n $N --steps 3 --warmup 1 --full --no-cpu-baseline --no-profile \
       > $OUT/sq$i.json 2> $OUT/sq$i.err || { echo "sq pass $i failed rc=$?"; exit 1; }
     echo "sq pass $i ok"
   done

@@ -16,7 +16,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--edge", "16", "--steps", "2", "--warmup", "1", "--reps", "3", "--no-box-state",
+# --full: the repetitions, per_rank and multi_gpu_parity are not part of a plain run
+ARGS = ["--gpus", "2", "--edge", "16", "--steps", "2", "--warmup", "1", "--full", "--reps", "3", "--no-box-state",
         "--no-clock-probe", "--no-copy-ceiling"]
 
 
@@ -116,3 +117,77 @@ def test_bench_rank_failure_ends_the_job(tmp_path):
     p = subprocess.run([sys.executable, "bench.py"] + ARGS, cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=300)
     assert p.returncode != 0 and not p.stdout.strip()
+
+
+PLAIN = ["--gpus", "1", "--edge", "16", "--steps", "2", "--warmup", "1"]
+
+
+def _oracle_state(n, steps):
+    """Inner nodes of the oracle's n^3 parity-random field after `steps` steps."""
+    from oracle import oracle as O
+    from tests.helpers import oracle_body
+    b = oracle_body(3, 2, [n] * 3)
+    b.pde[:] = 0.0
+    O.fill_random(b, [n] * 3, 0x5EED)
+    for _ in range(steps):
+        for s in range(3):
+            b.stage(s, 0.9)
+    return b.pde.reshape(b.shape_all + (9,))[2:-2, 2:-2, 2:-2]
+
+
+def test_plain_run_times_the_steps_once_and_measures_nothing_else(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: the headline fields, one timing
+    of the K steps, and none of what --full adds."""
+    d = _run([sys.executable, "bench.py"] + PLAIN, _env(tmp_path))
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1
+    assert d["reps"] == 1 and d["rep_ms_per_step"] == [d["ms_per_step"]] and d["ms_per_step"] > 0
+    assert d["unit"] == "Mnode-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["metric"].endswith("16³ CubicGrid")
+    # value and ms_per_step are the same measurement (both rounded on the line)
+    assert d["value"] == pytest.approx(16 ** 3 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-2, abs=0.11)
+    for k in ("roofline", "cpu_baseline", "multi_gpu_parity", "per_rank", "process_state"):
+        assert d[k] is None, k
+    assert "outputs" not in d
+
+
+def test_dump_outputs_is_the_state_after_warmup_plus_steps(tmp_path):
+    """--dump-outputs writes the inner nodes the last timed step left: with the
+    stub backend exactly the oracle after W + K steps (so --steps sets the number
+    of timed steps), float64, and the same from run to run."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py"] + PLAIN + ["--dump-outputs", str(tmp_path / name)], _env(tmp_path))
+        assert d["outputs"]["file"] == "state.npy" and d["outputs"]["shape"] == [16, 16, 16, 9]
+        assert os.listdir(tmp_path / name) == ["state.npy"]
+        outs.append(np.load(tmp_path / name / "state.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == (16, 16, 16, 9)
+    assert np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[0], _oracle_state(16, 1 + 2))
+
+
+def test_full_run_dumps_the_last_repetitions_state(tmp_path):
+    """With --full the K steps are repeated; the dump is the state after all of them."""
+    import numpy as np
+    d = _run([sys.executable, "bench.py"] + PLAIN + ["--full", "--reps", "2", "--no-box-state", "--no-clock-probe",
+                                                     "--no-copy-ceiling", "--no-cpu-baseline",
+                                                     "--dump-outputs", str(tmp_path / "o")], _env(tmp_path))
+    assert d["full"] is True and d["reps"] == 2 and d["roofline"]["kernel"] == "fused_xyz"
+    assert np.array_equal(np.load(tmp_path / "o" / "state.npy"), _oracle_state(16, 1 + 2 * 2))
+
+
+def test_dump_boxes_fit_the_budget_and_the_slab():
+    """The sample of a slab too large to dump whole: 8 cubes inside the slab,
+    within the byte budget, both corners among them, the same on every call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for sizes in ([512, 512, 512], [128, 128, 128], [64, 512, 512], [20, 1024, 1024]):
+        for world in (1, 2, 8):
+            budget = bench.DUMP_BYTES // world
+            origins, edge = bench.dump_boxes(sizes, budget)
+            assert (origins, edge) == bench.dump_boxes(sizes, budget)
+            assert len(origins) == bench.DUMP_BOXES and 1 <= edge <= min(sizes)
+            assert len(origins) * edge ** 3 * 9 * 8 <= budget
+            assert origins[0] == [0, 0, 0] and origins[1] == [s - edge for s in sizes]
+            assert all(0 <= o[d] and o[d] + edge <= sizes[d] for o in origins for d in range(3))
+    assert bench.dump_boxes([512] * 3, bench.DUMP_BYTES)[1] == 48

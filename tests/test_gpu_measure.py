@@ -33,7 +33,7 @@ def test_bench_prints_one_json_line_with_rccl_self():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "64", "--steps", "3",
-                        "--warmup", "1", "--reps", "2", "--rccl-self", "--no-cpu-baseline",
+                        "--warmup", "1", "--full", "--reps", "2", "--rccl-self", "--no-cpu-baseline",
                         "--no-copy-ceiling", "--no-clock-probe"],
                        capture_output=True, text=True, timeout=200, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -63,3 +63,49 @@ def test_bench_refuses_more_ranks_than_gpus():
                        capture_output=True, text=True, timeout=100, cwd=root, env=env)
     assert r.returncode != 0 and not r.stdout.strip()
     assert "refusing to run fewer ranks" in r.stderr
+
+
+@pytest.mark.timeout(120)
+def test_plain_bench_dumps_the_boxes_of_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` on a
+    128^3 grid (151 MB of inner nodes: over the 64 MB budget, so the dump is the
+    8 sample boxes copied out on the device): ONE JSON line with the headline
+    fields and nothing --full adds, and every box equal, bitwise, to the same
+    nodes of a context stepped W + K times here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import gcm_amd
+    from gcm_amd.host import isotropic_elastic_matrices
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    n, k, w = 128, 2, 1
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--n", str(n), "--steps", str(k),
+                        "--warmup", str(w), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=100, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["reps"] == 1 and d["steps"] == k and d["ms_per_step"] > 0
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["process_state"] is None
+    origins, edge = bench.dump_boxes([n] * 3, bench.DUMP_BYTES)
+    assert edge == 48 and d["outputs"]["origins"] == origins
+    got = np.load(tmp_path / "state.npy")
+    assert got.dtype == np.float64 and got.shape == (8, edge, edge, edge, 9)
+    assert got.nbytes <= 64_000_000
+    U, U1, L = isotropic_elastic_matrices(3, 4.0, 2.0, 1.0)
+    c = gcm_amd.Context(3, 2, [n] * 3)
+    try:
+        c.set_materials(U[None], U1[None], L[None])
+        c.fill_random([n] * 3, 0x5EED)
+        for _ in range(w + k):
+            c.step(0.9)
+        want = c.download().reshape((n + 4,) * 3 + (9,))[2:-2, 2:-2, 2:-2]
+    finally:
+        c.close()
+    for i, (x, y, z) in enumerate(origins):
+        assert np.array_equal(got[i], want[x:x + edge, y:y + edge, z:z + edge]), f"box {i} at {(x, y, z)}"
