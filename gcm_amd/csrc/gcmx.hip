@@ -19,6 +19,7 @@
 #include "../../include/gcmx.h"
 #include "common.hpp"
 #include "launch.hpp"
+#include "ortho.hpp"
 
 using namespace gcmx;
 static_assert(GCMX_MAX_BORDER_Q == kMaxBorderQ, "border quantity limit");
@@ -149,6 +150,9 @@ struct gcmx_ctx {
 	bool het_ok = false;           // this tau: floor(q) = 0 and equal axes for every material
 	std::vector<IsoAxis> het_iso;  // [mat]: tau-independent part (axis 0)
 	IsoAxis* het_d = nullptr;      // [mat] on the device, per tau
+	bool ortho_fast = false;       // 3-D, homogeneous, unrotated orthotropic structure (k_step_ortho)
+	bool ortho_ok = false;         // this tau: every pair's feet lie on the sides the kernel reads
+	OrthoAxis ortho[3] = {};       // per-axis values (tau part in build_tables)
 	bool ghosts_touched = false;   // node-list border fills / contact copies / ghost uploads happened
 	bool last_ode_fused = false;   // the last gcmx_step_ode scaled the stresses in the step's epilogue
 	unsigned faces_written = 0;    // faces (bit 2*axis + side) whose ghosts a face fill wrote
@@ -343,6 +347,24 @@ gcmx_status build_tables(gcmx_ctx* c, double tau) {
 			A.kf2 = t.kf[2];
 			lagrange_weights(A.c1, A.kf1 == 0 ? bs : 0, A.w1);
 			lagrange_weights(A.c2, A.kf2 == 0 ? bs : 0, A.w2);
+		}
+	}
+	if (c->ortho_fast) {
+		// per pair p the feet 2p (+s side) and 2p+1 (-s side) share q; a step that
+		// puts them elsewhere (tau <= 0) takes the generic stages
+		c->ortho_ok = true;
+		for (int s = 0; s < D; s++) {
+			const AxisTable& t = h[s];
+			OrthoAxis& A = c->ortho[s];
+			for (int p = 0; p < 3; p++) {
+				const int k = 2 * p;
+				if (t.kf[k] != t.kf[k + 1] || std::memcmp(t.coef[k], t.coef[k + 1], sizeof(t.coef[k])) != 0)
+					return fail(GCMX_ERR_STATE, "inconsistent foot data");
+				if (t.shift[k] != 1 || t.shift[k + 1] != -1 || t.zero_q[k] || t.zero_q[k + 1]) c->ortho_ok = false;
+				for (int i = 0; i < 3; i++) A.c[p][i] = i < bs ? t.coef[k][i] : 0.0;
+				A.kf[p] = t.kf[k];
+				lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
+			}
 		}
 	}
 	HIP_TRY(hipMemcpyAsync(c->tabs_d, h.data(), h.size() * sizeof(AxisTable),
@@ -758,6 +780,41 @@ gcmx_status halo_ensure(gcmx_ctx* c) {
 	return halo_wait(c);
 }
 
+}  // namespace
+
+// The unrotated orthotropic pattern (ortho.hpp), entry by entry: exact zeros
+// where the structure has none, velocity entries exactly 1.0 (U) / 0.5 (U1),
+// unit entries of the zero rows / columns exactly 1.0, rows 2p / 2p+1 (columns
+// of U1) with exactly opposite stress coefficients, every material value
+// finite and non-zero (k_stage_generic skips a zero entry; the one-pass kernel
+// would multiply by it), L = (-v, +v) within a pair and L[6..8] == 0.
+bool gcmx::ortho_axis_extract(int s, const double* U, const double* U1, const double* L, OrthoAxis& A) {
+	if (s < 0 || s > 2) return false;
+	bool seen[16] = {};
+	double* slots[16] = {&A.a[0], &A.a[1], &A.a[2], nullptr, &A.g[0], &A.g[1], nullptr, nullptr,
+	                     &A.p[0], &A.p[1], &A.p[2], nullptr, &A.e[0], &A.e[1], nullptr, nullptr};
+	auto entry = [&](const Coef& co, double v) {
+		if (co.slot == kZero) return v == 0.0;
+		if (co.slot == kOne) return v == 1.0;
+		if (co.slot == kHalf) return v == 0.5;
+		const int i = co.slot - kOA;
+		const double m = co.sign > 0 ? v : -v;
+		if (!std::isfinite(m) || m == 0.0) return false;
+		if (seen[i]) return *slots[i] == m;
+		seen[i] = true;
+		*slots[i] = m;
+		return true;
+	};
+	for (int k = 0; k < 9; k++)
+		for (int j = 0; j < 9; j++)
+			if (!entry(ortho_u(s, k, j), U[k * 9 + j]) || !entry(ortho_u1(s, k, j), U1[k * 9 + j])) return false;
+	for (int p = 0; p < 3; p++)
+		if (!(L[2 * p] < 0) || !(L[2 * p + 1] == -L[2 * p]) || !std::isfinite(L[2 * p])) return false;
+	return L[6] == 0.0 && L[7] == 0.0 && L[8] == 0.0;
+}
+
+namespace {
+
 // Fast kernels: 3-D, one material, no per-node ids, isotropic zero pattern.
 void refresh_fast(gcmx_ctx* c) {
 	const int D = c->D, M = c->M;
@@ -783,6 +840,14 @@ void refresh_fast(gcmx_ctx* c) {
 		}
 	c->iso_het = het;
 	c->het_ok = false;
+	// the orthotropic one-pass step: tried only when the isotropic pattern failed
+	// (isotropic matrices never match it: their row order differs)
+	bool ortho = !fits && D == 3 && c->mat_d == nullptr && c->n_mat == 1 && onepass_layout_ok(c->geo);
+	for (int sx = 0; ortho && sx < D; sx++)
+		ortho = ortho_axis_extract(sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M], &c->L[(size_t)sx * M],
+		                           c->ortho[sx]);
+	c->ortho_fast = ortho;
+	c->ortho_ok = ortho;
 	c->tabs_tau = NAN;
 }
 
@@ -810,6 +875,11 @@ gcmx_path effective_path(gcmx_ctx* c) {
 		return GCMX_PATH_FUSED;
 	}
 	if (c->D == 2) return step2d_admissible(c) ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
+	if (c->ortho_fast) {  // the one-pass orthotropic step or the generic stages
+		const bool onepass = c->ortho_ok && c->bs <= 3 && ortho_supported(c->geo) && !c->ghosts_touched &&
+		                     c->faces_written == 0 && (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
+		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
+	}
 	if (c->D != 3 || !c->iso_fast || c->bs > 3) return GCMX_PATH_GENERIC;
 	if (c->path == GCMX_PATH_GENERIC) return GCMX_PATH_GENERIC;
 	// the per-stage kernels address whole layers with 32-bit offsets
@@ -860,7 +930,7 @@ gcmx_status stage_impl(gcmx_ctx* c, int axis, double tau) {
 	const double bytes = node_stage_bytes(c) * (double)g.n_inner;
 	// no per-stage het kernels; the per-stage kernels of the split path are 3-D only
 	const gcmx_path p =
-	    (c->iso_het || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC : effective_path(c);
+	    (c->iso_het || c->ortho_fast || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC : effective_path(c);
 	bool ok;
 	if (p == GCMX_PATH_GENERIC) {
 		Timed t(c, "stage_generic", bytes, c->stream);
@@ -1489,6 +1559,10 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 	const bool halo = has_halo(c);
 	auto xyz = [&](const char* name, int x0, int x1, hipStream_t st, int rows, int xb0 = 0, int xb1 = 0) {
 		Timed t(c, name, plane_bytes * ((x1 - x0) + (xb1 - xb0)), st);
+		if (c->ortho_fast) {  // effective_path admitted it: no face conditions, no folded ODE
+			auto launch_o = c->fp_mode == GCMX_FP_EXACT ? ortho_exact::launch_step_ortho : ortho_fma::launch_step_ortho;
+			return fb == nullptr && launch_o(c->cur, c->nxt, g, c->ortho, x0, x1, st, rows, &t.kname, xb0, xb1);
+		}
 		const HetMaterials het{c->het_d, c->mat_d};
 		auto launch = c->fp_mode == GCMX_FP_EXACT ? xyz_exact::launch_fused_xyz : xyz_fma::launch_fused_xyz;
 		return launch(c->cur, c->nxt, g, c->iso, x0, x1, st, rows, fb, &t.kname, c->iso_het ? &het : nullptr,
@@ -1618,7 +1692,7 @@ gcmx_status ode_upload(gcmx_ctx* c, const std::vector<double>& f);
 // node's own read from LDS).  Call after build_tables (het_ok is per tau).
 bool ode_foldable(const gcmx_ctx* c, const StepOde& ode) {
 	// rows longer than 512: only the z split has the store epilogue (uniform medium)
-	if (!ode.on || c->bs > 2 || (c->geo.sizes[2] > 512 && !(!c->mat_d && zs_admissible(c->geo, c->iso))))
+	if (!ode.on || c->ortho_fast || c->bs > 2 || (c->geo.sizes[2] > 512 && !(!c->mat_d && zs_admissible(c->geo, c->iso))))
 		return false;
 	if (!c->mat_d) return ode.f.size() == 1;
 	return c->iso_het && c->het_ok && (int)ode.f.size() <= kHetMaxMaterials;
@@ -1784,7 +1858,7 @@ gcmx_status step_faces_body(gcmx_ctx* c, double tau, const gcmx_face* faces, con
 	// One pass: x faces in memory, y/z faces as FaceBC; the y/z faces must be
 	// free of PRESSURE (its trace needs components the fused ghosts do not form)
 	// and no face may hold ghosts written earlier but not refreshed now.
-	bool fused = D == 3 && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && !c->ortho_fast && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	FaceBC fb{};
@@ -1930,7 +2004,7 @@ static gcmx_status step_face_map_body(gcmx_ctx* c, double tau, const gcmx_face_m
 	launch_set_face_tables(m->bq_d, m->fc_d, t, c->stream);
 	HIP_TRY(hipGetLastError());
 	c->last_ode_fused = false;
-	bool fused = D == 3 && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && !c->ortho_fast && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	for (int f = 2; f < 2 * D && fused; f++)
@@ -2003,6 +2077,11 @@ gcmx_status gcmx_set_kernel_path(gcmx_ctx* c, gcmx_path p) {
 	if (p < GCMX_PATH_AUTO || p > GCMX_PATH_FUSED) return fail(GCMX_ERR_INVALID_ARG, "bad path");
 	c->path = p;
 	return GCMX_OK;
+}
+
+int gcmx_matrix_structure(gcmx_ctx* c) {
+	if (!c || c->n_mat <= 0) return 0;
+	return (c->iso_fast || c->iso2_fast || c->iso_het) ? 1 : c->ortho_fast ? 2 : 0;
 }
 
 gcmx_path gcmx_effective_path(gcmx_ctx* c) { return c ? effective_path(c) : GCMX_PATH_GENERIC; }

@@ -1,0 +1,195 @@
+// ortho.hpp -- structure of the unrotated orthotropic-elastic stage
+// (ElasticModel<3>::constructNotRotated, ElasticModel3D.cpp:286-429) for the
+// one-pass orthotropic step (kernels_ortho.hip), beside iso.hpp's isotropic one.
+//
+// Per axis S the decomposition has three characteristic pairs (rows 2p, 2p+1 of
+// U, p = 0, 1: shear, p = 2: longitudinal), each reading one velocity and one
+// stress component at the feet, with L = (-, +) within a pair, and three zero
+// modes that read node values only:
+//
+//   axis | pair 0         | pair 1         | pair 2         | rows 6, 7, 8 read
+//   x    | (Vy, Sxy, c66) | (Vz, Sxz, c55) | (Vx, Sxx, c11) | g0 Sxx + Syy; Syz; g1 Sxx + Szz
+//   y    | (Vx, Sxy, c66) | (Vz, Syz, c44) | (Vy, Syy, c22) | Sxx + g0 Syy; Sxz; g1 Syy + Szz
+//   z    | (Vx, Sxz, c55) | (Vy, Syz, c44) | (Vz, Szz, c33) | Sxx + g0 Szz; Sxy; Syy + g1 Szz
+//
+// The components read at the feet are the isotropic stage's (iso_window); the
+// row order, the coefficients and the three distinct speeds per axis are not.
+#pragma once
+
+#include "iso.hpp"
+
+namespace gcmx {
+
+// Per-axis values of the orthotropic step, passed by value (kernel arguments).
+struct OrthoAxis {
+	double a[3];     // U:  stress entry of row 2p (row 2p+1 carries -a[p])
+	double g[2];     // U:  the longitudinal-stress entries of rows 6 and 8
+	double p[3];     // U1: stress-row entry of column 2p (column 2p+1 carries -p[p])
+	double e[2];     // U1: column 4 entries of the rows of rows 6 / 8's unit components (column 5: -e)
+	double c[3][3];  // per pair: ((q - i) + 1) / i, i = 1..bs
+	double w[3][3];  // per pair: the interpolant's Lagrange weights (lagrange_weights)
+	int kf[3];       // per pair: floor(q)
+	int pad_;
+};
+static_assert(sizeof(OrthoAxis) == 28 * 8 + 4 * 4, "OrthoAxis has padding");
+
+// Succeeds only for the exact pattern above (see the definition, gcmx.hip).
+bool ortho_axis_extract(int s, const double* U, const double* U1, const double* L, OrthoAxis& A);
+
+// The one-pass orthotropic step of planes [x0, x1) and, when xb1 > xb0, of a
+// second range [xb0, xb1) (a second launch).  `a`: the three axes; `chunk`: y
+// rows per block (0 = automatic).  Needs ortho_supported(g), y/z ghosts of both
+// layers zero, x ghost planes of `in` valid.  Two builds, as kernels_xyz.hip's.
+bool ortho_supported(const Geo& g);  // fused_supported(g), and Z <= 512 at borderSize 3
+namespace ortho_exact {
+bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
+                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0);
+}
+namespace ortho_fma {
+bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
+                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0);
+}
+
+// ----------------------------------------------------------- structure --
+
+// Slots of the material values (beside iso.hpp's kZero / kOne / kHalf).
+enum OrthoSlot : int { kOA = 16, kOG = 20, kOP = 24, kOE = 28 };  // + index
+
+// Velocity / stress component of pair P; the stress components no pair reads,
+// ascending (rows 6, 7, 8 carry a unit entry there).
+__host__ __device__ constexpr int opair_vel(int S, int P) {
+	return S == 0 ? (P == 0 ? 1 : P == 1 ? 2 : 0) : S == 1 ? (P == 0 ? 0 : P == 1 ? 2 : 1) : P;
+}
+__host__ __device__ constexpr int opair_sig(int S, int P) {
+	return sig3(S, opair_vel(S, P));
+}
+__host__ __device__ constexpr int ozero_comp(int S, int i) {
+	return S == 0 ? (i == 0 ? 6 : i == 1 ? 7 : 8) : S == 1 ? (i == 0 ? 3 : i == 1 ? 5 : 8) : (i == 0 ? 3 : i == 1 ? 4 : 6);
+}
+
+// U(k, j): rows are eigenstrings.
+__host__ __device__ constexpr Coef ortho_u(int S, int k, int j) {
+	if (k < 6) {
+		const int p = k / 2;
+		return j == opair_vel(S, p) ? Coef{kOne, 1} : j == opair_sig(S, p) ? Coef{kOA + p, (k & 1) ? -1 : 1} : cz();
+	}
+	if (j == ozero_comp(S, k - 6)) return Coef{kOne, 1};
+	if (k != 7 && j == opair_sig(S, 2)) return Coef{kOG + (k == 8), 1};
+	return cz();
+}
+
+// U1(c, n): columns are eigenvectors.
+__host__ __device__ constexpr Coef ortho_u1(int S, int c, int n) {
+	for (int p = 0; p < 3; p++) {
+		if (c == opair_vel(S, p)) return (n == 2 * p || n == 2 * p + 1) ? Coef{kHalf, 1} : cz();
+		if (c == opair_sig(S, p)) return n == 2 * p ? Coef{kOP + p, 1} : n == 2 * p + 1 ? Coef{kOP + p, -1} : cz();
+	}
+	for (int i = 0; i < 3; i++)
+		if (c == ozero_comp(S, i)) {
+			if (n == 6 + i) return Coef{kOne, 1};
+			if (i != 1 && n == 4) return Coef{kOE + (i == 2), 1};
+			if (i != 1 && n == 5) return Coef{kOE + (i == 2), -1};
+		}
+	return cz();
+}
+
+// Components read at the neighbours (rows 0..5) / only at the node (rows 6..8).
+__host__ __device__ constexpr unsigned ortho_window(int S) {
+	unsigned m = 0;
+	for (int p = 0; p < 3; p++) m |= bit(opair_vel(S, p)) | bit(opair_sig(S, p));
+	return m;
+}
+__host__ __device__ constexpr unsigned ortho_center_only(int S) {
+	return bit(ozero_comp(S, 0)) | bit(ozero_comp(S, 1)) | bit(ozero_comp(S, 2));
+}
+static_assert(ortho_window(0) == iso_window(0) && ortho_window(1) == iso_window(1) &&
+                  ortho_window(2) == iso_window(2),
+              "the orthotropic stages read the isotropic window components");
+
+// u * v for a structural entry; exact w.r.t. the reference product fl(u * v).
+template <int SLOT, int SIGN>
+__device__ __forceinline__ double oterm(const OrthoAxis& A, double v) {
+	double m;
+	if constexpr (SLOT == kOne) m = v;
+	else if constexpr (SLOT == kHalf) m = v * 0.5;
+	else if constexpr (SLOT >= kOE) m = A.e[SLOT - kOE] * v;
+	else if constexpr (SLOT >= kOP) m = A.p[SLOT - kOP] * v;
+	else if constexpr (SLOT >= kOG) m = A.g[SLOT - kOG] * v;
+	else m = A.a[SLOT - kOA] * v;
+	return SIGN > 0 ? m : -m;
+}
+
+// Unrolled sum over j of U(k, j) * V(j) (or U1(c, n) * r(n)) in ascending index
+// order, skipping structural zeros, starting from the first non-zero term.
+template <int S, bool ISU1, int ROW, int J = 0>
+struct ORowSum {
+	template <class F>
+	__device__ __forceinline__ static double go(const OrthoAxis& A, F val, double acc, bool first) {
+		if constexpr (J == 9) {
+			return acc;
+		} else {
+			constexpr Coef c = ISU1 ? ortho_u1(S, ROW, J) : ortho_u(S, ROW, J);
+			if constexpr (c.slot == kZero) {
+				return ORowSum<S, ISU1, ROW, J + 1>::go(A, val, acc, first);
+			} else {
+				const double t = oterm<c.slot, c.sign>(A, val(J));
+				return ORowSum<S, ISU1, ROW, J + 1>::go(A, val, first ? t : acc + t, false);
+			}
+		}
+	}
+};
+
+// Rows 2P (L < 0: foot on the +S side) and 2P+1 (-S side) of r = diag(U * V).
+// W(j, o): component j at offset o along S (|o| <= BS).
+template <int S, int BS, bool KF0, int P, class WF>
+__device__ __forceinline__ void opair_update(const OrthoAxis& A, WF W, double& ra, double& rb) {
+	const double* coef = A.c[P];
+	const double* wts = A.w[P];
+	const int kf = A.kf[P];
+	auto interp = [&](int j, int sh) {
+		double sv[BS + 1];
+#pragma unroll
+		for (int i = 0; i <= BS; i++) sv[i] = W(j, sh * i);
+		if constexpr (GCMX_LAGRANGE && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
+		else return newton_minmax<BS, KF0>(sv, kf, coef);
+	};
+	ra = ORowSum<S, false, 2 * P>::go(A, [&](int j) { return interp(j, 1); }, 0.0, true);
+	rb = ORowSum<S, false, 2 * P + 1>::go(A, [&](int j) { return interp(j, -1); }, 0.0, true);
+}
+
+// Rows 6..8 (q == 0: the interpolant is the node value itself).  C(j): node value.
+template <int S, class CF>
+__device__ __forceinline__ void ocenter_update(const OrthoAxis& A, CF C, double (&r)[9]) {
+	r[6] = ORowSum<S, false, 6>::go(A, C, 0.0, true);
+	r[7] = ORowSum<S, false, 7>::go(A, C, 0.0, true);
+	r[8] = ORowSum<S, false, 8>::go(A, C, 0.0, true);
+}
+
+// out = U1 * r (localGcmStep's second product).
+template <int S>
+__device__ __forceinline__ void ou1_apply(const OrthoAxis& A, const double (&r)[9], double (&out)[9]) {
+	auto rv = [&](int n) { return r[n]; };
+	out[0] = ORowSum<S, true, 0>::go(A, rv, 0.0, true);
+	out[1] = ORowSum<S, true, 1>::go(A, rv, 0.0, true);
+	out[2] = ORowSum<S, true, 2>::go(A, rv, 0.0, true);
+	out[3] = ORowSum<S, true, 3>::go(A, rv, 0.0, true);
+	out[4] = ORowSum<S, true, 4>::go(A, rv, 0.0, true);
+	out[5] = ORowSum<S, true, 5>::go(A, rv, 0.0, true);
+	out[6] = ORowSum<S, true, 6>::go(A, rv, 0.0, true);
+	out[7] = ORowSum<S, true, 7>::go(A, rv, 0.0, true);
+	out[8] = ORowSum<S, true, 8>::go(A, rv, 0.0, true);
+}
+
+// One node's stage.  W(j, o): window component j at offset o along S
+// (|o| <= BS); C(j): node value of a component rows 6..8 read.
+template <int S, int BS, bool KF0, class WF, class CF>
+__device__ __forceinline__ void onode_update(const OrthoAxis& A, WF W, CF C, double (&out)[9]) {
+	double r[9];
+	opair_update<S, BS, KF0, 0>(A, W, r[0], r[1]);
+	opair_update<S, BS, KF0, 1>(A, W, r[2], r[3]);
+	opair_update<S, BS, KF0, 2>(A, W, r[4], r[5]);
+	ocenter_update<S>(A, C, r);
+	ou1_apply<S>(A, r, out);
+}
+
+}  // namespace gcmx

@@ -36,7 +36,7 @@ QUANTITY_CODES = {"Vx": 2, "Vy": 3, "Vz": 4, "Sxx": 5, "Sxy": 6, "Sxz": 7, "Syy"
 # Exported symbols, in header order (checked by tests/test_abi.py).
 SYMBOLS = [
     "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_status_string",
-    "gcmx_create", "gcmx_destroy", "gcmx_set_materials", "gcmx_set_material_ids",
+    "gcmx_create", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
     "gcmx_upload", "gcmx_download", "gcmx_fill_random", "gcmx_stage", "gcmx_step",
     "gcmx_set_kernel_path", "gcmx_set_step_schedule", "gcmx_set_fp_mode", "gcmx_get_fp_mode", "gcmx_effective_path", "gcmx_last_step_path",
     "gcmx_border_fill",
@@ -114,6 +114,8 @@ def lib() -> ctypes.CDLL:
     L.gcmx_destroy.argtypes = [vp]
     L.gcmx_destroy.restype = None
     L.gcmx_set_materials.argtypes = [vp, ctypes.c_int, dp, dp, dp]
+    L.gcmx_matrix_structure.argtypes = [vp]
+    L.gcmx_matrix_structure.restype = ctypes.c_int
     L.gcmx_set_material_ids.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
     L.gcmx_upload.argtypes = [vp, dp]
     L.gcmx_download.argtypes = [vp, dp]
@@ -314,6 +316,10 @@ class Context:
     def fp_mode(self, mode: int):
         """gcmx_set_fp_mode: the one-pass step's floating-point build."""
         _check(lib().gcmx_set_fp_mode(self._ptr, mode))
+
+    def matrix_structure(self) -> int:
+        """gcmx_matrix_structure: 0 general, 1 isotropic, 2 unrotated orthotropic."""
+        return int(lib().gcmx_matrix_structure(self._ptr))
 
     @property
     def effective_path(self) -> str:

@@ -21,6 +21,10 @@ def lib() -> ctypes.CDLL:
         L.gcm_host_isotropic_elastic_matrices.argtypes = [ctypes.c_int, ctypes.c_double,
                                                           ctypes.c_double, ctypes.c_double,
                                                           dp, dp, dp]
+        L.gcm_host_orthotropic_elastic_matrices.argtypes = [ctypes.c_double, dp, dp, dp, dp]
+        L.gcm_host_orthotropic_from_isotropic.argtypes = [ctypes.c_double, ctypes.c_double,
+                                                          ctypes.c_double, dp]
+        L.gcm_host_orthotropic_from_isotropic.restype = None
         _lib = L
     return _lib
 
@@ -33,3 +37,23 @@ def isotropic_elastic_matrices(D: int, rho: float, lam: float, mu: float):
     if lib().gcm_host_isotropic_elastic_matrices(D, rho, lam, mu, dp(U), dp(U1), dp(L)) != 0:
         raise ValueError("bad isotropic material (needs rho > 0, mu > 0)")
     return U, U1, L
+
+
+def orthotropic_elastic_matrices(rho: float, c):
+    """ElasticModel<3>::constructGcmMatrices for an unrotated OrthotropicMaterial
+    (c = c11, c12, c13, c22, c23, c33, c44, c55, c66): U, U1 [3,9,9], L [3,9]."""
+    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+    if c.shape[0] != 9:
+        raise ValueError("c must hold the nine elastic constants")
+    U = np.zeros((3, 9, 9)); U1 = np.zeros((3, 9, 9)); L = np.zeros((3, 9))
+    dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    if lib().gcm_host_orthotropic_elastic_matrices(rho, dp(c), dp(U), dp(U1), dp(L)) != 0:
+        raise ValueError("bad orthotropic material (needs rho > 0 and positive diagonal constants)")
+    return U, U1, L
+
+
+def orthotropic_from_isotropic(rho: float, lam: float, mu: float) -> np.ndarray:
+    """OrthotropicMaterial(IsotropicMaterial): c11, c12, c13, c22, c23, c33, c44, c55, c66."""
+    c = np.zeros(9)
+    lib().gcm_host_orthotropic_from_isotropic(rho, lam, mu, c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return c

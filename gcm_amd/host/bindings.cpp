@@ -112,6 +112,14 @@ struct PyEngine {
 		else c = as<3>().getMesh(id)->ctx();
 		return gcmx_last_ode_fused(c) != 0;
 	}
+	/// Structure the device recognised in the body's matrices (gcmx_matrix_structure).
+	int matrixStructure(size_t id) {
+		gcmx_ctx* c = nullptr;
+		if (D == 1) c = as<1>().getMesh(id)->ctx();
+		else if (D == 2) c = as<2>().getMesh(id)->ctx();
+		else c = as<3>().getMesh(id)->ctx();
+		return gcmx_matrix_structure(c);
+	}
 	real maximalEigenvalue(size_t id) {
 		if (D == 1) return as<1>().getMesh(id)->getMaximalEigenvalue();
 		if (D == 2) return as<2>().getMesh(id)->getMaximalEigenvalue();
@@ -254,6 +262,16 @@ struct PySimplexEngine {
 
 }  // namespace
 
+/// Nine elastic constants and optional rotation angles -> OrthotropicMaterial.
+std::shared_ptr<OrthotropicMaterial> makeOrthotropic(real rho, const std::vector<real>& c, real tau0, int number,
+                                                     const std::array<real, 3>& angles) {
+	if (c.size() != 9) throw Exception("c must hold c11, c12, c13, c22, c23, c33, c44, c55, c66");
+	auto m = std::make_shared<OrthotropicMaterial>(
+	    rho, std::initializer_list<real>{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]}, 0, 0, angles, tau0);
+	m->materialNumber = number;
+	return m;
+}
+
 PYBIND11_MODULE(_gcm_host, m) {
 	m.doc() = "C++ host mirror of libgcm's cubic Engine/Task surface over the gcmx C-ABI";
 	py::register_exception<Exception>(m, "GcmException");
@@ -278,6 +296,11 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         [](Task& t, size_t id, std::vector<int> sizes, std::vector<int> start) {
 		         t.bodies[id] = Task::Body();
 		         t.cubicGrid.cubics[id] = {sizes, start};
+		         // a body added after an orthotropic material that covers it is of that kind
+		         const auto& mc = t.materialConditions;
+		         if (mc.type == Task::MaterialCondition::Type::BY_AREAS ? mc.byAreas.defaultOrthotropic != nullptr
+		                                                                  : mc.byBodies.bodyOrthotropicMap.count(id) > 0)
+			         t.bodies[id].materialId = Materials::T::ORTHOTROPIC;
 	         })
 	    .def("set_default_material",
 	         [](Task& t, real rho, real lam, real mu, real tau0, int number) {
@@ -301,6 +324,33 @@ PYBIND11_MODULE(_gcm_host, m) {
 		             std::make_shared<IsotropicMaterial>(rho, lam, mu, 0, 0, 0, tau0);
 	         },
 	         py::arg("id"), py::arg("rho"), py::arg("lam"), py::arg("mu"), py::arg("tau0") = 0.0)
+	    .def("set_default_orthotropic_material",
+	         [](Task& t, real rho, std::vector<real> c, real tau0, int number, std::array<real, 3> angles) {
+		         t.materialConditions.type = Task::MaterialCondition::Type::BY_AREAS;
+		         t.materialConditions.byAreas.defaultOrthotropic = makeOrthotropic(rho, c, tau0, number, angles);
+		         for (auto& b : t.bodies) b.second.materialId = Materials::T::ORTHOTROPIC;
+	         },
+	         "Default OrthotropicMaterial (c = c11, c12, c13, c22, c23, c33, c44, c55, c66); every body "
+	         "becomes Materials::ORTHOTROPIC (3-D, unrotated only)",
+	         py::arg("rho"), py::arg("c"), py::arg("tau0") = 0.0, py::arg("number") = 0,
+	         py::arg("angles") = std::array<real, 3>{0, 0, 0})
+	    .def("add_orthotropic_material",
+	         [](Task& t, py::tuple area, real rho, std::vector<real> c, real tau0, int number,
+	            std::array<real, 3> angles) {
+		         t.materialConditions.byAreas.materials.push_back(
+		             {makeArea(area), nullptr, makeOrthotropic(rho, c, tau0, number, angles)});
+		         for (auto& b : t.bodies) b.second.materialId = Materials::T::ORTHOTROPIC;
+	         },
+	         py::arg("area"), py::arg("rho"), py::arg("c"), py::arg("tau0") = 0.0, py::arg("number") = 0,
+	         py::arg("angles") = std::array<real, 3>{0, 0, 0})
+	    .def("set_body_orthotropic_material",
+	         [](Task& t, size_t id, real rho, std::vector<real> c, real tau0, std::array<real, 3> angles) {
+		         t.materialConditions.type = Task::MaterialCondition::Type::BY_BODIES;
+		         t.materialConditions.byBodies.bodyOrthotropicMap[id] = makeOrthotropic(rho, c, tau0, 0, angles);
+		         if (t.bodies.count(id)) t.bodies[id].materialId = Materials::T::ORTHOTROPIC;
+	         },
+	         py::arg("id"), py::arg("rho"), py::arg("c"), py::arg("tau0") = 0.0,
+	         py::arg("angles") = std::array<real, 3>{0, 0, 0})
 	    .def_property("output_directory", [](Task& t) { return t.globalSettings.outputDirectory; },
 	                  [](Task& t, const std::string& d) { t.globalSettings.outputDirectory = d; })
 	    .def("add_snapshotter",
@@ -613,6 +663,7 @@ PYBIND11_MODULE(_gcm_host, m) {
 	    .def("path", &PyEngine::path)
 	    .def("last_path", &PyEngine::lastPath)
 	    .def("ode_fused", &PyEngine::odeFused)
+	    .def("matrix_structure", &PyEngine::matrixStructure, "0 general, 1 isotropic, 2 orthotropic")
 	    .def("sync", &PyEngine::sync, py::arg("body") = 0)
 	    .def("maximal_eigenvalue", &PyEngine::maximalEigenvalue)
 	    .def_property_readonly("steps", [](PyEngine& p) { return p.e->stepsDone(); })

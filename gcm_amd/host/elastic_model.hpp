@@ -1,4 +1,5 @@
-// elastic_model.hpp -- host-side GcmMatrices for isotropic elastic media.
+// elastic_model.hpp -- host-side GcmMatrices for isotropic and unrotated
+// orthotropic elastic media.
 //
 // Mirrors rheology/models/ElasticModel.hpp:57-65, 362-553 (constructGcmMatrices,
 // constructGcmMatrix, constructEigenvectors, constructEigenstrings) for the
@@ -6,10 +7,20 @@
 // the host; the device only ever sees the finished U / U1 / L tables.  Every
 // expression keeps the reference's evaluation order so the tables are bitwise
 // the reference's (checked against the oracle in tests/test_abi.py::test_host_matrices_match_oracle_bitwise).
+//
+// Orthotropic media (rheology/materials/OrthotropicMaterial.hpp,
+// ElasticModel3D.cpp:286-429, constructNotRotated): 3-D only, and only with the
+// material's main axes along the coordinate axes (anglesOfRotation == 0), where
+// the decomposition is written out in closed form.  Rotated media need the
+// reference's cubic-equation solver (ElasticModel3D.cpp:86-283), 2-D orthotropic
+// matrices its 2-D restriction; neither is here, and both throw gcm::Exception,
+// as does D = 1 (the reference throws there too).
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
+#include <initializer_list>
 #include <cstring>
 #include <stdexcept>
 #include <type_traits>
@@ -17,6 +28,11 @@
 namespace gcm {
 
 using real = double;
+
+/// gcm::Exception analogue: every reference assert_* / THROW_* throws.
+struct Exception : std::runtime_error {
+	using std::runtime_error::runtime_error;
+};
 
 constexpr int pdeSize(int D) { return D + D * (D + 1) / 2; }
 
@@ -35,11 +51,51 @@ struct IsotropicMaterial {
 	      tau0(tau0_) {}
 };
 
+/// Orthotropic material (rheology/materials/OrthotropicMaterial.hpp:9-64).
+struct OrthotropicMaterial {
+	real rho = 0;  ///< density
+	union {
+		real c[9];  ///< elastic coefficients
+		struct {
+			real c11, c12, c13, c22, c23, c33, c44, c55, c66;
+		};
+	};
+	real yieldStrength = 0;             ///< plasticity parameter
+	real continualDamageParameter = 0;  ///< parameter in the continual damage equation
+	real tau0 = 0;                      ///< viscosity parameter (decay time)
+	/// the main axes of the material are rotated from the global basis by these angles
+	std::array<real, 3> anglesOfRotation = {0, 0, 0};
+	int materialNumber = 0;
+
+	/// OrthotropicMaterial.cpp:7-18
+	OrthotropicMaterial(const IsotropicMaterial& isotropic) {
+		anglesOfRotation = {0, 0, 0};
+		rho = isotropic.rho;
+		yieldStrength = isotropic.yieldStrength;
+		continualDamageParameter = isotropic.continualDamageParameter;
+		tau0 = isotropic.tau0;
+		c11 = c22 = c33 = isotropic.lambda + 2 * isotropic.mu;
+		c44 = c55 = c66 = isotropic.mu;
+		c12 = c13 = c23 = isotropic.lambda;
+		materialNumber = isotropic.materialNumber;
+	}
+	/// OrthotropicMaterial.cpp:21-32: c11, c12, c13, c22, c23, c33, c44, c55, c66
+	OrthotropicMaterial(real rho_ = 0, std::initializer_list<real> list = {0, 0, 0, 0, 0, 0, 0, 0, 0},
+	                    real yieldStrength_ = 0, real continualDamageParameter_ = 0,
+	                    const std::array<real, 3>& phi = {0, 0, 0}, real tau0_ = 0)
+	    : rho(rho_), yieldStrength(yieldStrength_), continualDamageParameter(continualDamageParameter_),
+	      tau0(tau0_), anglesOfRotation(phi) {
+		if (list.size() != 9) throw Exception("OrthotropicMaterial needs nine elastic constants");
+		std::copy(list.begin(), list.end(), c);
+	}
+};
+
 /// GcmMatrices<M,D>::GcmMatrix (util/math/GridCharacteristicMethod.hpp:40-52), row-major.
 template <int D>
 struct GcmMatrices {
 	static constexpr int M = pdeSize(D);
 	struct GcmMatrix {
+		std::array<real, M * M> A{};  ///< filled by the orthotropic construction only
 		std::array<real, M * M> U{}, U1{};
 		std::array<real, M> L{};
 		real getMaximalEigenvalue() const {
@@ -224,6 +280,132 @@ struct ElasticModel {
 			detail::localBasisOf<D>(n, basis);
 			constructGcmMatrix(out.m[i], mat, basis);
 		}
+	}
+
+	/// constructGcmMatrices for an orthotropic material with anglesOfRotation == 0
+	/// (ElasticModel3D.cpp:432-449 -> constructNotRotated, :286-429): A, L, U, U1 of
+	/// the three axes, every expression in the order the reference writes it.
+	static void constructGcmMatrices(Matrices& out, const OrthotropicMaterial& mat) {
+		if constexpr (D != 3) {
+			(void)out;
+			(void)mat;
+			throw Exception("orthotropic media are implemented in 3-D only");
+		} else {
+			for (int i = 0; i < 3; i++)
+				if (mat.anglesOfRotation[i] != 0)
+					throw Exception("rotated orthotropic media are not implemented (anglesOfRotation must be 0)");
+			if (!(mat.rho > 0) || !(mat.c11 > 0) || !(mat.c22 > 0) || !(mat.c33 > 0) || !(mat.c44 > 0) ||
+			    !(mat.c55 > 0) || !(mat.c66 > 0))
+				throw Exception("orthotropic material needs rho > 0 and c11, c22, c33, c44, c55, c66 > 0");
+			constructNotRotated(out, mat.rho, mat.c11, mat.c12, mat.c13, mat.c22, mat.c23, mat.c33, mat.c44,
+			                    mat.c55, mat.c66);
+		}
+	}
+
+	/// ElasticModel<3>::constructNotRotated (ElasticModel3D.cpp:286-429)
+	static void constructNotRotated(Matrices& m, const real rho, const real c11, const real c12, const real c13,
+	                                const real c22, const real c23, const real c33, const real c44,
+	                                const real c55, const real c66) {
+		static_assert(D == 3, "3-D only");
+		using std::sqrt;
+		m.m[0].A = {
+		    0, 0, 0, -1.0 / rho, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, -1.0 / rho, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, -1.0 / rho, 0, 0, 0,
+		    -c11, 0, 0, 0, 0, 0, 0, 0, 0,
+		    0, -c66, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, -c55, 0, 0, 0, 0, 0, 0,
+		    -c12, 0, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 0, 0,
+		    -c13, 0, 0, 0, 0, 0, 0, 0, 0};
+		m.m[0].L = {-sqrt(c66 / rho), sqrt(c66 / rho), -sqrt(c55 / rho), sqrt(c55 / rho),
+		            -sqrt(c11 / rho), sqrt(c11 / rho), 0, 0, 0};
+		m.m[0].U = {
+		    0, 1.0, 0, 0, 1.0 / (sqrt(c66) * sqrt(rho)), 0, 0, 0, 0,
+		    0, 1.0, 0, 0, -1.0 / (sqrt(c66) * sqrt(rho)), 0, 0, 0, 0,
+		    0, 0, 1.0, 0, 0, 1.0 / (sqrt(c55) * sqrt(rho)), 0, 0, 0,
+		    0, 0, 1.0, 0, 0, -1.0 / (sqrt(c55) * sqrt(rho)), 0, 0, 0,
+		    1.0, 0, 0, 1.0 / (sqrt(c11) * sqrt(rho)), 0, 0, 0, 0, 0,
+		    1.0, 0, 0, -1.0 / (sqrt(c11) * sqrt(rho)), 0, 0, 0, 0, 0,
+		    0, 0, 0, -c12 / c11, 0, 0, 1.0, 0, 0.0,
+		    0, 0, 0, 0, 0, 0, 0, 1.0, 0,
+		    0, 0, 0, -(1.0 * c13) / c11, 0, 0, 0, 0, 1.0};
+		m.m[0].U1 = {
+		    0, 0, 0, 0, 0.5, 0.5, 0, 0, 0,
+		    0.5, 0.5, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0.5, 0.5, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0.5 * sqrt(c11) * sqrt(rho), -0.5 * sqrt(c11) * sqrt(rho), 0, 0, 0,
+		    0.5 * sqrt(c66) * sqrt(rho), -0.5 * sqrt(c66) * sqrt(rho), 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0.5 * sqrt(c55) * sqrt(rho), -0.5 * sqrt(c55) * sqrt(rho), 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, (0.5 * c12 * sqrt(rho)) / sqrt(c11), -(0.5 * c12 * sqrt(rho)) / sqrt(c11), 1, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 1, 0,
+		    0, 0, 0, 0, (0.5 * c13 * sqrt(rho)) / sqrt(c11), -(0.5 * c13 * sqrt(rho)) / sqrt(c11), 0, 0, 1};
+
+		m.m[1].A = {
+		    0, 0, 0, 0, -1.0 / rho, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, -1.0 / rho, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, -1.0 / rho, 0,
+		    0, -c12, 0, 0, 0, 0, 0, 0, 0,
+		    -c66, 0, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 0, 0,
+		    0, -c22, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, -c44, 0, 0, 0, 0, 0, 0,
+		    0, -c23, 0, 0, 0, 0, 0, 0, 0};
+		m.m[1].L = {-sqrt(c66 / rho), sqrt(c66 / rho), -sqrt(c44 / rho), sqrt(c44 / rho),
+		            -sqrt(c22 / rho), sqrt(c22 / rho), 0, 0, 0};
+		m.m[1].U = {
+		    1.0, 0, 0, 0, 1.0 / (sqrt(c66) * sqrt(rho)), 0, 0, 0, 0,
+		    1.0, 0, 0, 0, -1.0 / (sqrt(c66) * sqrt(rho)), 0, 0, 0, 0,
+		    0, 0, 1.0, 0, 0, 0, 0, 1.0 / (sqrt(c44) * sqrt(rho)), 0,
+		    0, 0, 1.0, 0, 0, 0, 0, -1.0 / (sqrt(c44) * sqrt(rho)), 0,
+		    0, 1.0, 0, 0, 0, 0, 1.0 / (sqrt(c22) * sqrt(rho)), 0, 0,
+		    0, 1.0, 0, 0, 0, 0, -1.0 / (sqrt(c22) * sqrt(rho)), 0, 0,
+		    0, 0, 0, 1.0, 0, 0, -c12 / c22, 0, 0.0,
+		    0, 0, 0, 0, 0, 1.0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, -(1.0 * c23) / c22, 0, 1.0};
+		m.m[1].U1 = {
+		    0.5, 0.5, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0.5, 0.5, 0, 0, 0,
+		    0, 0, 0.5, 0.5, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, (0.5 * c12) / sqrt(c22 / rho), -(0.5 * c12) / sqrt(c22 / rho), 1, 0, 0,
+		    0.5 * sqrt(c66) * sqrt(rho), -0.5 * sqrt(c66) * sqrt(rho), 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 1, 0,
+		    0, 0, 0, 0, 0.5 * sqrt(c22) * sqrt(rho), -0.5 * sqrt(c22) * sqrt(rho), 0, 0, 0,
+		    0, 0, 0.5 * sqrt(c44) * sqrt(rho), -0.5 * sqrt(c44) * sqrt(rho), 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, (0.5 * c23 * sqrt(rho)) / sqrt(c22), -(0.5 * c23 * sqrt(rho)) / sqrt(c22), 0, 0, 1};
+
+		m.m[2].A = {
+		    0, 0, 0, 0, 0, -1.0 / rho, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, -1.0 / rho, 0,
+		    0, 0, 0, 0, 0, 0, 0, 0, -1.0 / rho,
+		    0, 0, -c13, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 0, 0,
+		    -c55, 0, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, -c23, 0, 0, 0, 0, 0, 0,
+		    0, -c44, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, -c33, 0, 0, 0, 0, 0, 0};
+		m.m[2].L = {-sqrt(c55 / rho), sqrt(c55 / rho), -sqrt(c44 / rho), sqrt(c44 / rho),
+		            -sqrt(c33 / rho), sqrt(c33 / rho), 0, 0, 0};
+		m.m[2].U = {
+		    1.0, 0, 0, 0, 0, 1.0 / (sqrt(c55) * sqrt(rho)), 0, 0, 0,
+		    1.0, 0, 0, 0, 0, -1.0 / (sqrt(c55) * sqrt(rho)), 0, 0, 0,
+		    0, 1.0, 0, 0, 0, 0, 0, 1.0 / (sqrt(c44) * sqrt(rho)), 0,
+		    0, 1.0, 0, 0, 0, 0, 0, -1.0 / (sqrt(c44) * sqrt(rho)), 0,
+		    0, 0, 1.0, 0, 0, 0, 0, 0, 1.0 / (sqrt(c33) * sqrt(rho)),
+		    0, 0, 1.0, 0, 0, 0, 0, 0, -1.0 / (sqrt(c33) * sqrt(rho)),
+		    0, 0, 0, 1.0, 0, 0, 0, 0, -(1.0 * c13) / c33,
+		    0, 0, 0, 0, 1.0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0, 0, 1.0, 0, -(1.0 * c23) / c33};
+		m.m[2].U1 = {
+		    0.5, 0.5, 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0.5, 0.5, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0.5, 0.5, 0, 0, 0,
+		    0, 0, 0, 0, (0.5 * c13 * sqrt(rho)) / sqrt(c33), -(0.5 * c13 * sqrt(rho)) / sqrt(c33), 1, 0, 0,
+		    0, 0, 0, 0, 0, 0, 0, 1, 0,
+		    0.5 * sqrt(c55) * sqrt(rho), -0.5 * sqrt(c55) * sqrt(rho), 0, 0, 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, (0.5 * c23 * sqrt(rho)) / sqrt(c33), -(0.5 * c23 * sqrt(rho)) / sqrt(c33), 0, 0, 1,
+		    0, 0, 0.5 * sqrt(c44) * sqrt(rho), -0.5 * sqrt(c44) * sqrt(rho), 0, 0, 0, 0, 0,
+		    0, 0, 0, 0, 0.5 * sqrt(c33) * sqrt(rho), -0.5 * sqrt(c33) * sqrt(rho), 0, 0, 0};
 	}
 
 	/// constructGcmMatrix + constructEigenvectors + constructEigenstrings

@@ -286,22 +286,47 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 	auto& matrices = st.matrices;
 
 	// ---- MaterialsCondition::apply (util/task/MaterialsCondition.hpp:23-36, 70-91)
-	std::vector<std::pair<std::shared_ptr<Area>, std::shared_ptr<IsotropicMaterial>>> conds;
+	// Body::materialId picks the kind every condition of the body is built with
+	// (the reference's factory choice, Engine.cpp:155-189)
+	typedef Task::MaterialCondition MC;
+	struct Cond {
+		std::shared_ptr<Area> first;
+		MC::Material iso;
+		MC::Orthotropic ortho;
+	};
+	std::vector<Cond> conds;
 	const auto& mc = task.materialConditions;
-	if (mc.type == Task::MaterialCondition::Type::BY_AREAS) {
-		conds.push_back({std::make_shared<InfiniteArea>(), mc.byAreas.defaultMaterial});
-		for (const auto& m : mc.byAreas.materials) conds.push_back({m.area, m.material});
+	const auto body = task.bodies.find(grid.id);
+	const Materials::T kind = body != task.bodies.end() ? body->second.materialId : Materials::T::ISOTROPIC;
+	if (mc.type == MC::Type::BY_AREAS) {
+		conds.push_back({std::make_shared<InfiniteArea>(), mc.byAreas.defaultMaterial, mc.byAreas.defaultOrthotropic});
+		for (const auto& m : mc.byAreas.materials) conds.push_back({m.area, m.material, m.orthotropic});
 	} else {
-		conds.push_back({std::make_shared<InfiniteArea>(), mc.byBodies.bodyMaterialMap.at(grid.id)});
+		const auto i = mc.byBodies.bodyMaterialMap.find(grid.id);
+		const auto o = mc.byBodies.bodyOrthotropicMap.find(grid.id);
+		if (i == mc.byBodies.bodyMaterialMap.end() && o == mc.byBodies.bodyOrthotropicMap.end())
+			throw std::out_of_range("no material for this body");
+		conds.push_back({std::make_shared<InfiniteArea>(),
+		                 i != mc.byBodies.bodyMaterialMap.end() ? i->second : nullptr,
+		                 o != mc.byBodies.bodyOrthotropicMap.end() ? o->second : nullptr});
 	}
 	if (conds.size() > 255) throw Exception("at most 255 material conditions per body");
 	matrices.assign(conds.size(), GcmMatrices<D>());
 	st.tau0.assign(conds.size(), 0);
 	for (size_t c = 0; c < conds.size(); c++) {
-		if (!conds[c].second) throw Exception("material condition without a material");
-		ElasticModel<D>::constructGcmMatrices(matrices[c], *conds[c].second);
-		st.tau0[c] = conds[c].second->tau0;
-		st.materialNumber.push_back(conds[c].second->materialNumber);
+		if (kind == Materials::T::ORTHOTROPIC) {
+			const MC::Orthotropic m = MC::orthotropicOf(conds[c].iso, conds[c].ortho);
+			if (!m) throw Exception("material condition without a material");
+			ElasticModel<D>::constructGcmMatrices(matrices[c], *m);
+			st.tau0[c] = m->tau0;
+			st.materialNumber.push_back(m->materialNumber);
+		} else {
+			if (conds[c].ortho) throw Exception("orthotropic material in an ISOTROPIC body (Body::materialId)");
+			if (!conds[c].iso) throw Exception("material condition without a material");
+			ElasticModel<D>::constructGcmMatrices(matrices[c], *conds[c].iso);
+			st.tau0[c] = conds[c].iso->tau0;
+			st.materialNumber.push_back(conds[c].iso->materialNumber);
+		}
 	}
 	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
 		const Real3 x = grid.coords(it);
@@ -321,11 +346,10 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 		ics.push_back({v.area, a});
 	}
 	{
-		GcmMatrices<D> front;  // mcConditions.front().material
-		ElasticModel<D>::constructGcmMatrices(front, *conds.front().second);
+		const GcmMatrices<D>& front = matrices.front();  // mcConditions.front().material
 		for (const auto& w : task.initialCondition.waves) {
 			if (!(w.direction >= 0 && w.direction < D)) throw Exception("wave direction out of range");
-			const int col = waveColumn(D, w.waveType);
+			const int col = waveColumn(D, w.waveType, kind);
 			std::array<real, M> tmp{};
 			for (int r = 0; r < M; r++) tmp[r] = front.m[w.direction].U1[r * M + col];
 			const real current = getQuantity(D, w.quantity, tmp.data());
@@ -643,8 +667,9 @@ void Engine<D>::createGridsAndContacts(const Task& task) {
 	if (task.bodies.size() != task.cubicGrid.cubics.size())
 		throw Exception("every body needs a cube");
 	for (const auto& tb : task.bodies) {
-		if (tb.second.materialId != Materials::T::ISOTROPIC || tb.second.modelId != Models::T::ELASTIC)
-			throw Exception("only isotropic elastic bodies are on this path");
+		if (tb.second.modelId != Models::T::ELASTIC) throw Exception("only elastic bodies are on this path");
+		if (tb.second.materialId == Materials::T::ORTHOTROPIC && D != 3)
+			throw Exception("orthotropic media are implemented in 3-D only");
 		Body body;
 		body.factory = std::make_shared<HipFactory<D>>(device);
 		const auto cp = constructionPack<D>(task, tb.first);

@@ -127,8 +127,8 @@ struct HostState {
 	std::vector<real> pde;
 	std::vector<uint8_t> matId;
 	std::vector<GcmMatrices<D>> matrices;
-	std::vector<real> tau0;  // IsotropicMaterial::tau0 per material condition
-	std::vector<int> materialNumber;  // IsotropicMaterial::materialNumber per condition
+	std::vector<real> tau0;  // tau0 of the material (either kind) per material condition
+	std::vector<int> materialNumber;  // its materialNumber per condition
 	real maximalEigenvalue = 0;
 };
 
@@ -344,7 +344,8 @@ public:
 	                                                       const Snapshotters::T type) = 0;
 };
 
-/// AbstractFactory<ElasticModel<D>, CubicGrid<D>, IsotropicMaterial, HipMesh>
+/// AbstractFactory<ElasticModel<D>, CubicGrid<D>, IsotropicMaterial, HipMesh>; a body whose
+/// Task::Body::materialId is ORTHOTROPIC is built with OrthotropicMaterial (buildHostState)
 template <int D>
 class HipFactory : public AbstractFactoryBase<D> {
 public:

@@ -32,4 +32,31 @@ int gcm_host_isotropic_elastic_matrices(int D, double rho, double lambda, double
 	}
 }
 
+/// ElasticModel<3>::constructGcmMatrices for an unrotated orthotropic material
+/// (c = c11, c12, c13, c22, c23, c33, c44, c55, c66): U, U1 [3][81] row-major,
+/// L [3][9].  Returns 0 or -1 (bad input).
+int gcm_host_orthotropic_elastic_matrices(double rho, const double* c, double* U, double* U1, double* L) {
+	try {
+		gcm::GcmMatrices<3> m;
+		gcm::ElasticModel<3>::constructGcmMatrices(
+		    m, gcm::OrthotropicMaterial(rho, {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]}));
+		for (int s = 0; s < 3; s++) {
+			for (int i = 0; i < 81; i++) {
+				U[s * 81 + i] = m.m[s].U[i];
+				U1[s * 81 + i] = m.m[s].U1[i];
+			}
+			for (int k = 0; k < 9; k++) L[s * 9 + k] = m.m[s].L[k];
+		}
+		return 0;
+	} catch (...) {
+		return -1;
+	}
+}
+
+/// OrthotropicMaterial(const IsotropicMaterial&): the nine constants, in constructor order.
+void gcm_host_orthotropic_from_isotropic(double rho, double lambda, double mu, double* c) {
+	const gcm::OrthotropicMaterial m(gcm::IsotropicMaterial(rho, lambda, mu));
+	for (int i = 0; i < 9; i++) c[i] = m.c[i];
+}
+
 }

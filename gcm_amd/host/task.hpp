@@ -19,10 +19,7 @@ namespace gcm {
 
 using Real3 = std::array<real, 3>;
 
-/// gcm::Exception analogue: every reference assert_* / THROW_* throws.
-struct Exception : std::runtime_error {
-	using std::runtime_error::runtime_error;
-};
+// gcm::Exception: elastic_model.hpp
 
 // ------------------------------------------------------------------ enums --
 // util/Enum.hpp:27-120 (same enumerator order: std::map iteration order of
@@ -155,10 +152,18 @@ inline void setQuantity(int D, PhysicalQuantities::T q, real value, real* v) {
 	if (c < 0) throw Exception("quantity not present in the PDE vector");
 	v[c] = value;
 }
-/// Column of U1 a wave type selects for isotropic media (Model.cpp:33-82).
-inline int waveColumn(int D, Waves::T w) {
+/// Column of U1 a wave type selects (Model.cpp:33-82): the enumerator's own
+/// value for isotropic media; for 3-D orthotropic media the pairs come shear
+/// first with L = (-, +) within a pair (Model.cpp:42-49).
+inline int waveColumn(int D, Waves::T w, Materials::T material = Materials::T::ISOTROPIC) {
 	const int col = static_cast<int>(w);
 	if (col >= 2 * D) throw Exception("wave type not present in this dimensionality");
+	if (material == Materials::T::ORTHOTROPIC) {
+		if (D != 3) throw Exception("orthotropic media are implemented in 3-D only");
+		// P_FORWARD, P_BACKWARD, S1_FORWARD, S1_BACKWARD, S2_FORWARD, S2_BACKWARD
+		static const int map[6] = {5, 4, 1, 0, 3, 2};
+		return map[col];
+	}
 	return col;
 }
 
@@ -195,20 +200,34 @@ struct Task {
 		std::map<size_t, Cube> cubics;
 	} cubicGrid;
 
+	/// Every condition holds a material of either kind: `material` (isotropic) or
+	/// `orthotropic`, the latter winning when both are set.  Body::materialId picks
+	/// the kind a body is built with (see orthotropicOf).
 	struct MaterialCondition {
 		typedef std::shared_ptr<IsotropicMaterial> Material;
+		typedef std::shared_ptr<OrthotropicMaterial> Orthotropic;
 		enum class Type { BY_AREAS, BY_BODIES } type = Type::BY_AREAS;
 		struct ByAreas {
 			Material defaultMaterial;
+			Orthotropic defaultOrthotropic;
 			struct Inhomogenity {
 				std::shared_ptr<Area> area;
 				Material material;
+				Orthotropic orthotropic = nullptr;
 			};
 			std::vector<Inhomogenity> materials;
 		} byAreas;
 		struct ByBodies {
 			std::map<size_t, Material> bodyMaterialMap;
+			std::map<size_t, Orthotropic> bodyOrthotropicMap;
 		} byBodies;
+		/// The material of one condition for an ORTHOTROPIC body: its orthotropic
+		/// material, or its isotropic one converted (OrthotropicMaterial.cpp:7-18).
+		static Orthotropic orthotropicOf(const Material& iso, const Orthotropic& ortho) {
+			if (ortho) return ortho;
+			if (iso) return std::make_shared<OrthotropicMaterial>(*iso);
+			return nullptr;
+		}
 	} materialConditions;
 
 	struct InitialCondition {

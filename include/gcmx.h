@@ -102,9 +102,17 @@ void        gcmx_destroy(gcmx_ctx* ctx);
  * (DefaultMesh.hpp:144) filled by MaterialsCondition::apply
  * (util/task/MaterialsCondition.hpp:23-36).  U/U1: [n_mat][dim][M*M] row-major,
  * L: [n_mat][dim][M] (GcmMatrices<M,D>::GcmMatrix {U, U1, L},
- * util/math/GridCharacteristicMethod.hpp:40-52).  n_mat in 1..255. */
+ * util/math/GridCharacteristicMethod.hpp:40-52).  n_mat in 1..255.
+ * Any matrices run (the generic per-stage kernel).  Two structures are
+ * recognised entry by entry and run faster kernels with identical results:
+ * the isotropic ElasticModel matrices, and, in 3-D with one material and no
+ * per-node ids, the unrotated orthotropic ones (ElasticModel3D.cpp:286-429:
+ * three characteristic pairs per axis with L = (-, +), shear pairs first). */
 gcmx_status gcmx_set_materials(gcmx_ctx* ctx, int n_mat, const double* U,
                                const double* U1, const double* L);
+/* Structure recognised in the matrices of the last gcmx_set_materials:
+ * 0 general, 1 isotropic, 2 unrotated orthotropic (0 before materials are set). */
+int         gcmx_matrix_structure(gcmx_ctx* ctx);
 /* One byte per node of the all-nodes array (getIndex order); NULL means every
  * node uses material 0.  Ghost entries are ignored.  With per-node ids the 3-D
  * step runs in one pass for up to 32 materials (their tables held in LDS, and
@@ -134,14 +142,19 @@ gcmx_status gcmx_stage(gcmx_ctx* ctx, int axis, double tau);
  * identical to dim consecutive gcmx_stage calls.  3-D: the one-pass step
  * (k_step_tx2 / k_fused_xyz); 2-D: the one-pass step k_step2d_iso / k_step2d
  * with one material, untouched ghosts and no X-slab exchange (else the
- * per-stage kernels); 1-D: the one stage. */
+ * per-stage kernels); 1-D: the one stage.  Orthotropic matrices
+ * (gcmx_matrix_structure 2): the one-pass step k_step_ortho when borderSize
+ * <= 3, 2 * borderSize <= Z <= 1024 (512 at borderSize 3), no ghost was ever written (border fills,
+ * face conditions, contact copies) and the path is AUTO or FUSED; otherwise,
+ * and in gcmx_stage, gcmx_step_faces and gcmx_step_face_map, the generic
+ * per-stage kernel.  gcmx_step_ode then scales in a separate pass. */
 gcmx_status gcmx_step(gcmx_ctx* ctx, double tau);
 gcmx_status gcmx_set_kernel_path(gcmx_ctx* ctx, gcmx_path path);
 /* Step schedule of the fused path and the fused kernel's y rows per block
  * (0 = automatic).  Results do not depend on either (tests/test_gpu_parity.py);
  * only the overlap of the X-slab halo exchange with compute does. */
 gcmx_status gcmx_set_step_schedule(gcmx_ctx* ctx, gcmx_schedule sched, int rows_per_block);
-/* The one-pass step's floating-point build (k_step_tx2 / k_fused_xyz; the
+/* The one-pass step's floating-point build (k_step_tx2 / k_fused_xyz / k_step_ortho; the
  * per-stage kernels always keep the reference's roundings).  Default FMA;
  * environment GCMX_FP=exact makes EXACT the default of new contexts. */
 gcmx_status gcmx_set_fp_mode(gcmx_ctx* ctx, gcmx_fp_mode mode);
