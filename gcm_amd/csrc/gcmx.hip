@@ -153,6 +153,10 @@ struct gcmx_ctx {
 	bool ortho_fast = false;       // 3-D, homogeneous, unrotated orthotropic structure (k_step_ortho)
 	bool ortho_ok = false;         // this tau: every pair's feet lie on the sides the kernel reads
 	OrthoAxis ortho[3] = {};       // per-axis values (tau part in build_tables)
+	bool ortho_het = false;        // per-node materials, every material of the orthotropic structure (k_step_ortho HET)
+	bool ortho_het_ok = false;     // this tau: every material's feet on the sides the kernel reads, floor(q) = 0
+	std::vector<OrthoAxis> ortho_het_h;  // [mat][3]: per-axis values (tau part in build_tables)
+	OrthoAxis* ortho_het_d = nullptr;    // [mat][3] on the device, per tau
 	bool ghosts_touched = false;   // node-list border fills / contact copies / ghost uploads happened
 	bool last_ode_fused = false;   // the last gcmx_step_ode scaled the stresses in the step's epilogue
 	unsigned faces_written = 0;    // faces (bit 2*axis + side) whose ghosts a face fill wrote
@@ -365,6 +369,31 @@ gcmx_status build_tables(gcmx_ctx* c, double tau) {
 				A.kf[p] = t.kf[k];
 				lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
 			}
+		}
+	}
+	if (c->ortho_het) {
+		// one OrthoAxis[3] per material, filled as the homogeneous branch fills its
+		// three; the one-pass step also needs floor(q) = 0 for every pair (KF0 only)
+		c->ortho_het_ok = true;
+		for (int m = 0; m < c->n_mat; m++)
+			for (int s = 0; s < D; s++) {
+				const AxisTable& t = h[(size_t)m * D + s];
+				OrthoAxis& A = c->ortho_het_h[(size_t)m * 3 + s];
+				for (int p = 0; p < 3; p++) {
+					const int k = 2 * p;
+					if (t.kf[k] != t.kf[k + 1] || std::memcmp(t.coef[k], t.coef[k + 1], sizeof(t.coef[k])) != 0)
+						return fail(GCMX_ERR_STATE, "inconsistent foot data");
+					if (t.shift[k] != 1 || t.shift[k + 1] != -1 || t.zero_q[k] || t.zero_q[k + 1] || t.kf[k] != 0)
+						c->ortho_het_ok = false;
+					for (int i = 0; i < 3; i++) A.c[p][i] = i < bs ? t.coef[k][i] : 0.0;
+					A.kf[p] = t.kf[k];
+					lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
+				}
+			}
+		if (c->ortho_het_ok) {  // the host copy lives in the context; synchronised below
+			if (!c->ortho_het_d) HIP_TRY(hipMalloc(&c->ortho_het_d, (size_t)kHetMaxMaterials * 3 * sizeof(OrthoAxis)));
+			HIP_TRY(hipMemcpyAsync(c->ortho_het_d, c->ortho_het_h.data(), c->ortho_het_h.size() * sizeof(OrthoAxis),
+			                       hipMemcpyHostToDevice, c->stream));
 		}
 	}
 	HIP_TRY(hipMemcpyAsync(c->tabs_d, h.data(), h.size() * sizeof(AxisTable),
@@ -848,6 +877,17 @@ void refresh_fast(gcmx_ctx* c) {
 		                           c->ortho[sx]);
 	c->ortho_fast = ortho;
 	c->ortho_ok = ortho;
+	// the same with per-node ids: every material of the orthotropic structure (a
+	// set that mixes it with isotropic-pattern materials stays general)
+	bool ohet = !het && D == 3 && c->mat_d != nullptr && c->n_mat >= 1 && c->n_mat <= kHetMaxMaterials &&
+	            onepass_layout_ok(c->geo);
+	c->ortho_het_h.assign(ohet ? (size_t)c->n_mat * 3 : 0, OrthoAxis{});
+	for (int m = 0; ohet && m < c->n_mat; m++)
+		for (int sx = 0; ohet && sx < D; sx++)
+			ohet = ortho_axis_extract(sx, &c->U[((size_t)m * D + sx) * M * M], &c->U1[((size_t)m * D + sx) * M * M],
+			                          &c->L[((size_t)m * D + sx) * M], c->ortho_het_h[(size_t)m * 3 + sx]);
+	c->ortho_het = ohet;
+	c->ortho_het_ok = false;
 	c->tabs_tau = NAN;
 }
 
@@ -875,6 +915,11 @@ gcmx_path effective_path(gcmx_ctx* c) {
 		return GCMX_PATH_FUSED;
 	}
 	if (c->D == 2) return step2d_admissible(c) ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
+	if (c->ortho_het) {  // per-node orthotropic materials: the homogeneous step's conditions, the HET instance set
+		const bool onepass = c->bs <= 3 && ortho_het_supported(c->geo) && !c->ghosts_touched && c->faces_written == 0 &&
+		                     (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
+		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
+	}
 	if (c->ortho_fast) {  // the one-pass orthotropic step or the generic stages
 		const bool onepass = c->ortho_ok && c->bs <= 3 && ortho_supported(c->geo) && !c->ghosts_touched &&
 		                     c->faces_written == 0 && (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
@@ -930,7 +975,8 @@ gcmx_status stage_impl(gcmx_ctx* c, int axis, double tau) {
 	const double bytes = node_stage_bytes(c) * (double)g.n_inner;
 	// no per-stage het kernels; the per-stage kernels of the split path are 3-D only
 	const gcmx_path p =
-	    (c->iso_het || c->ortho_fast || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC : effective_path(c);
+	    (c->iso_het || c->ortho_fast || c->ortho_het || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC
+	                                                                                          : effective_path(c);
 	bool ok;
 	if (p == GCMX_PATH_GENERIC) {
 		Timed t(c, "stage_generic", bytes, c->stream);
@@ -1312,6 +1358,7 @@ void gcmx_destroy(gcmx_ctx* c) {
 	(void)hipFree(c->nodes_d);
 	(void)hipFree(c->ode_d);
 	(void)hipFree(c->het_d);
+	(void)hipFree(c->ortho_het_d);
 	if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
 	if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
 	if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -1559,9 +1606,11 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 	const bool halo = has_halo(c);
 	auto xyz = [&](const char* name, int x0, int x1, hipStream_t st, int rows, int xb0 = 0, int xb1 = 0) {
 		Timed t(c, name, plane_bytes * ((x1 - x0) + (xb1 - xb0)), st);
-		if (c->ortho_fast) {  // effective_path admitted it: no face conditions, no folded ODE
+		if (c->ortho_fast || c->ortho_het) {  // effective_path admitted it: no face conditions, no folded ODE
 			auto launch_o = c->fp_mode == GCMX_FP_EXACT ? ortho_exact::launch_step_ortho : ortho_fma::launch_step_ortho;
-			return fb == nullptr && launch_o(c->cur, c->nxt, g, c->ortho, x0, x1, st, rows, &t.kname, xb0, xb1);
+			const OrthoHet ohet{c->ortho_het_d, c->mat_d, c->n_mat, 0};  // this context's own inner nodes' ids
+			return fb == nullptr && launch_o(c->cur, c->nxt, g, c->ortho, x0, x1, st, rows, &t.kname, xb0, xb1,
+			                                 c->ortho_het ? &ohet : nullptr);
 		}
 		const HetMaterials het{c->het_d, c->mat_d};
 		auto launch = c->fp_mode == GCMX_FP_EXACT ? xyz_exact::launch_fused_xyz : xyz_fma::launch_fused_xyz;
@@ -1692,7 +1741,7 @@ gcmx_status ode_upload(gcmx_ctx* c, const std::vector<double>& f);
 // node's own read from LDS).  Call after build_tables (het_ok is per tau).
 bool ode_foldable(const gcmx_ctx* c, const StepOde& ode) {
 	// rows longer than 512: only the z split has the store epilogue (uniform medium)
-	if (!ode.on || c->ortho_fast || c->bs > 2 || (c->geo.sizes[2] > 512 && !(!c->mat_d && zs_admissible(c->geo, c->iso))))
+	if (!ode.on || c->ortho_fast || c->ortho_het || c->bs > 2 || (c->geo.sizes[2] > 512 && !(!c->mat_d && zs_admissible(c->geo, c->iso))))
 		return false;
 	if (!c->mat_d) return ode.f.size() == 1;
 	return c->iso_het && c->het_ok && (int)ode.f.size() <= kHetMaxMaterials;
@@ -1737,7 +1786,8 @@ gcmx_status step_body(gcmx_ctx* c, double tau, const StepOde& ode) {
 		if (s) return s;
 		return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
 	}
-	if (effective_path(c) != GCMX_PATH_FUSED || c->faces_written != 0 || (c->iso_het && !c->het_ok)) {
+	if (effective_path(c) != GCMX_PATH_FUSED || c->faces_written != 0 || (c->iso_het && !c->het_ok) ||
+	    (c->ortho_het && !c->ortho_het_ok)) {
 		for (int a = 0; a < c->D; a++) {
 			s = stage_impl(c, a, tau);
 			if (s) return s;
@@ -1858,7 +1908,7 @@ gcmx_status step_faces_body(gcmx_ctx* c, double tau, const gcmx_face* faces, con
 	// One pass: x faces in memory, y/z faces as FaceBC; the y/z faces must be
 	// free of PRESSURE (its trace needs components the fused ghosts do not form)
 	// and no face may hold ghosts written earlier but not refreshed now.
-	bool fused = D == 3 && !c->ortho_fast && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	FaceBC fb{};
@@ -2004,7 +2054,7 @@ static gcmx_status step_face_map_body(gcmx_ctx* c, double tau, const gcmx_face_m
 	launch_set_face_tables(m->bq_d, m->fc_d, t, c->stream);
 	HIP_TRY(hipGetLastError());
 	c->last_ode_fused = false;
-	bool fused = D == 3 && !c->ortho_fast && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	for (int f = 2; f < 2 * D && fused; f++)
@@ -2081,7 +2131,7 @@ gcmx_status gcmx_set_kernel_path(gcmx_ctx* c, gcmx_path p) {
 
 int gcmx_matrix_structure(gcmx_ctx* c) {
 	if (!c || c->n_mat <= 0) return 0;
-	return (c->iso_fast || c->iso2_fast || c->iso_het) ? 1 : c->ortho_fast ? 2 : 0;
+	return (c->iso_fast || c->iso2_fast || c->iso_het) ? 1 : (c->ortho_fast || c->ortho_het) ? 2 : 0;
 }
 
 gcmx_path gcmx_effective_path(gcmx_ctx* c) { return c ? effective_path(c) : GCMX_PATH_GENERIC; }

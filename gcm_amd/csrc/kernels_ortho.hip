@@ -47,11 +47,38 @@ namespace GCMX_ORTHO_NS {
 // Precondition: every y/z ghost of both layers is zero, so the intermediate
 // results at ghost rows / columns are the constant 0.0; x ghost planes of `in`
 // are valid.  Lanes z >= Z shadow column Z-1 and store 0.0 into the first z ghost.
-template <int BS, int ZT, bool KF0>
-__global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double* __restrict__ in,
-                                                                   double* __restrict__ outl, Geo g, OrthoAxis AX,
-                                                                   OrthoAxis AY, OrthoAxis AZ, int x0, int chunk,
-                                                                   int nplanes) {
+//
+// HET: per-node materials (GridCharacteristicMethod::stage takes each node's own
+// matrices; the neighbours only supply values).  The materials' tables
+// (het.n x 3 OrthoAxis, 720 B each) are copied into LDS at block start, one
+// barrier before first use, so the row loop reads no table through global
+// memory or the kernel arguments.  The id of row r (one byte
+// per inner node, linear [x][y][z], no ghosts) is loaded with that row's first
+// X-stage pair and travels to the row's Y and Z stages in a register ring
+// beside `cen`; 145 B/node/step.  Rows >= Y (zero ghost rows, clamp_row) take
+// the id of row Y-1 and lanes z >= Z that of column Z-1: any valid material maps
+// a zero row to zero, a stray byte would index LDS past the tables.  AX/AY/AZ
+// are unused; KF0 only (every pair of every axis of every material).  The
+// per-lane coefficients live in VGPRs, so these instances are compiled for two
+// waves per SIMD up to ZT = 512 (ortho_min_waves); instances: ortho_het_built.
+//
+// The LDS tables of one instance: declared only in the HET instantiation (the
+// homogeneous instances keep their LDS size), one array per kernel instance.
+template <int BS, int ZT, bool HET>
+__device__ __forceinline__ OrthoAxis (*ortho_lds_tables())[3] {
+	if constexpr (HET) {
+		__shared__ OrthoAxis t[kHetMaxMaterials][3];
+		return t;
+	} else {
+		return nullptr;
+	}
+}
+
+template <int BS, int ZT, bool KF0, bool HET = false>
+__global__ __launch_bounds__(ZT, ortho_min_waves(BS, ZT, HET)) void k_step_ortho(
+    const double* __restrict__ in, double* __restrict__ outl, Geo g, OrthoAxis AX, OrthoAxis AY, OrthoAxis AZ, int x0,
+    int chunk, int nplanes, OrthoHet het) {
+	static_assert(!HET || KF0, "the heterogeneous step is built for floor(q) = 0 only");
 	constexpr unsigned WMX = ortho_window(0);
 	constexpr unsigned CMX = ortho_center_only(0);
 	constexpr unsigned WMY = ortho_window(1);
@@ -89,6 +116,32 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 	const Planes src(in + pbase, g.cs);
 	const PlanesW out_p(outl + pbase, g.cs);
 
+	// HET: the tables into LDS; ax(S, m): axis S of material m
+	OrthoAxis(*const tabs)[3] = ortho_lds_tables<BS, ZT, HET>();
+	[[maybe_unused]] const uint8_t* idp = nullptr;
+	if constexpr (HET) {
+		typedef unsigned long long u64;
+		static_assert(sizeof(OrthoAxis) % sizeof(u64) == 0, "OrthoAxis is copied in 8-byte words");
+		const int nw = het.n * 3 * (int)(sizeof(OrthoAxis) / sizeof(u64));
+		const u64* ts = reinterpret_cast<const u64*>(het.tab);
+		u64* td = reinterpret_cast<u64*>(&tabs[0][0]);
+		for (int i = z; i < nw; i += ZT) td[i] = ts[i];
+		idp = het.ids + ((long long)x * Y) * Z + zc;
+	}
+	// the id of inner node (x, r, zc), r clamped into the id array (no ghosts)
+	auto id_load = [&](int r) -> int {
+		if constexpr (HET) return idp[(unsigned)(r < Y - 1 ? r : Y - 1) * (unsigned)Z];
+		else return 0;
+	};
+	auto ax = [&](auto SC, [[maybe_unused]] int m) -> const OrthoAxis& {
+		constexpr int S = decltype(SC)::value;
+		if constexpr (HET) return tabs[m][S];
+		else return S == 0 ? AX : S == 1 ? AY : AZ;
+	};
+	using S0 = std::integral_constant<int, 0>;
+	using S1 = std::integral_constant<int, 1>;
+	using S2 = std::integral_constant<int, 2>;
+
 	if (z < 2 * BS) {  // ghost slots of both LDS row buffers: zero, never overwritten
 		const int gslot = (z < BS) ? z : (Z + z);
 #pragma unroll
@@ -97,6 +150,7 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 			lds[1][q][gslot] = 0.0;
 		}
 	}
+	if constexpr (HET) __syncthreads();  // the tables, before the prologue's X stages
 
 	// X stage of row r, loaded one characteristic pair (velocity + stress
 	// windows) at a time with the next pair in flight.
@@ -119,7 +173,8 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 	using P2 = std::integral_constant<int, 2>;
 	// wa holds pair 0 of row r (already issued); loads pairs 1, 2 and the
 	// node-only components as it goes.
-	auto x_stage_rest = [&](PairWin& wa, int r, double (&xr)[9]) {
+	auto x_stage_rest = [&](PairWin& wa, int r, double (&xr)[9], int m) {
+		const OrthoAxis& AX = ax(S0{}, m);
 		const unsigned o = base + (unsigned)r * sty;
 		PairWin wb;
 		pair_load(P1{}, wb, o);
@@ -149,7 +204,11 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 	// y..y+BS wait in a small delay line.
 	double win[NWY][W];
 	double cen[BS + 1][NCY];
-	auto push = [&](const double (&xr)[9], int slot) {  // slot: window index of the row
+	[[maybe_unused]] int idr[BS + 1];  // HET: ids of rows y..y+BS
+	auto push = [&](const double (&xr)[9], int slot, [[maybe_unused]] int m) {  // slot: window index of the row
+		if constexpr (HET) {
+			if (slot >= BS) idr[slot - BS] = m;
+		}
 #pragma unroll
 		for (int j = 0; j < 9; j++) {
 			if ((WMY >> j) & 1u) win[wslot(WMY, j)][slot] = xr[j];
@@ -164,15 +223,17 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 	for (int k = 0; k < W; k++) {
 		const int r = yb - BS + k;
 		double xr[9];
+		int m = 0;
 		if (r >= 0 && r < Y) {
 			PairWin wa;
 			x_load_a(wa, r);
-			x_stage_rest(wa, r, xr);
+			m = id_load(r);
+			x_stage_rest(wa, r, xr, m);
 		} else {
 #pragma unroll
 			for (int j = 0; j < 9; j++) xr[j] = 0.0;
-		}
-		push(xr, k);
+		}  // (a zero row's id is never used: the Y and Z stages run for rows < Y only)
+		push(xr, k, m);
 	}
 	// in-loop X rows are loaded without a branch: rows past Y are zero ghost rows
 	// (their X stage is 0.0), clamped into the plane's allocated ghost rows
@@ -182,23 +243,29 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 	int buf = 0;
 	for (int y = yb; y < ye; y++) {
 		double yv[9];
+		int m_y = 0;
+		if constexpr (HET) m_y = idr[0];
+		const OrthoAxis& AYn = ax(S1{}, m_y);
+		const OrthoAxis& AZn = ax(S2{}, m_y);
 		onode_update<1, BS, KF0>(
-		    AY, [&](int j, int o) { return win[wslot(WMY, j)][BS + o]; },
+		    AYn, [&](int j, int o) { return win[wslot(WMY, j)][BS + o]; },
 		    [&](int j) { return ((WMY >> j) & 1u) ? win[wslot(WMY, j)][BS] : cen[0][wslot(CMY, j)]; }, yv);
 #pragma unroll
 		for (int j = 0; j < 9; j++)
 			if ((WMZ >> j) & 1u) lds[buf][wslot(WMZ, j)][BS + z] = live ? yv[j] : 0.0;
 		PairWin wa_next;
+		[[maybe_unused]] int m_next = 0;
 		__syncthreads();
 		{
 			double zv[9];
 			onode_update<2, BS, KF0>(
-			    AZ, [&](int j, int o) { return lds[buf][wslot(WMZ, j)][BS + z + o]; },
+			    AZn, [&](int j, int o) { return lds[buf][wslot(WMZ, j)][BS + z + o]; },
 			    [&](int j) { return ((WMZ >> j) & 1u) ? lds[buf][wslot(WMZ, j)][BS + z] : yv[j]; }, zv);
 			const unsigned offo = plane + (unsigned)y * sty + zo;
 			// next row's first pair: loads older than this row's stores
 			sched_fence();
 			x_load_a(wa_next, clamp_row(y + BS + 1));
+			if constexpr (HET) m_next = id_load(y + BS + 1);
 			sched_fence();
 #pragma unroll
 			for (int c = 0; c < 9; c++) out_p.st_nt(c, offo, live ? zv[c] : 0.0);
@@ -212,11 +279,15 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 		for (int k = 0; k < BS; k++)
 #pragma unroll
 			for (int q = 0; q < NCY; q++) cen[k][q] = cen[k + 1][q];
+		if constexpr (HET) {
+#pragma unroll
+			for (int k = 0; k < BS; k++) idr[k] = idr[k + 1];
+		}
 		{  // X stage of row y+BS+1 (zero ghost rows give zero) -> window slot W-1
 			double xr[9];
 			sched_fence();
-			x_stage_rest(wa_next, clamp_row(y + BS + 1), xr);
-			push(xr, W - 1);
+			x_stage_rest(wa_next, clamp_row(y + BS + 1), xr, m_next);
+			push(xr, W - 1, m_next);
 			sched_fence();
 		}
 	}
@@ -225,10 +296,10 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? 2 : 4) void k_step_ortho(const double
 // ------------------------------------------------------------- launchers --
 
 // The instance a launch runs, as a readable symbol (gcmx_profile_kernel).
-template <int BS, int ZT, bool KF0>
+template <int BS, int ZT, bool KF0, bool HET = false>
 static const char* ortho_name() {
 	static const std::string s = "k_step_ortho<" + std::to_string(BS) + ", " + std::to_string(ZT) + ", " +
-	                             (KF0 ? "KF0" : "!KF0") + GCMX_FP_TAG + ">";
+	                             (KF0 ? "KF0" : "!KF0") + (HET ? ", HET" : "") + GCMX_FP_TAG + ">";
 	return s.c_str();
 }
 
@@ -245,39 +316,52 @@ static int ortho_chunk_for(int Y, int nplanes, int req) {
 
 template <int BS, int ZT>
 static void launch_ortho_t(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
-                           hipStream_t st, int req_chunk, const char** kname) {
+                           hipStream_t st, int req_chunk, const char** kname, const OrthoHet* het) {
+	const int chunk = ortho_chunk_for(g.sizes[1], x1 - x0, req_chunk);
+	const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * (x1 - x0));
+	if (het) {  // per-node materials: the caller checked floor(q) = 0 for every material
+		if constexpr (ortho_het_built(BS, ZT)) {
+			const OrthoAxis none{};
+			hipLaunchKernelGGL((k_step_ortho<BS, ZT, true, true>), grid, dim3(ZT), 0, st, in, out, g, none, none, none,
+			                   x0, chunk, x1 - x0, *het);
+			*kname = ortho_name<BS, ZT, true, true>();
+		}
+		return;
+	}
 	bool kf0 = true;
 	for (int s = 0; s < 3; s++)
 		for (int p = 0; p < 3; p++) kf0 = kf0 && a[s].kf[p] == 0;
-	const int chunk = ortho_chunk_for(g.sizes[1], x1 - x0, req_chunk);
-	const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * (x1 - x0));
+	const OrthoHet nohet{};
 	if (kf0) {
 		hipLaunchKernelGGL((k_step_ortho<BS, ZT, true>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1], a[2], x0,
-		                   chunk, x1 - x0);
+		                   chunk, x1 - x0, nohet);
 		*kname = ortho_name<BS, ZT, true>();
 	} else {
 		hipLaunchKernelGGL((k_step_ortho<BS, ZT, false>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1], a[2], x0,
-		                   chunk, x1 - x0);
+		                   chunk, x1 - x0, nohet);
 		*kname = ortho_name<BS, ZT, false>();
 	}
 }
 
 template <int BS>
 static void launch_ortho_bs(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
-                            hipStream_t st, int ch, const char** kn) {
+                            hipStream_t st, int ch, const char** kn, const OrthoHet* het) {
 	const int Z = g.sizes[2];
-	if (Z <= 64) launch_ortho_t<BS, 64>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 128) launch_ortho_t<BS, 128>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 256) launch_ortho_t<BS, 256>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 512) launch_ortho_t<BS, 512>(in, out, g, a, x0, x1, st, ch, kn);
-	else if constexpr (BS <= 2) launch_ortho_t<BS, 1024>(in, out, g, a, x0, x1, st, ch, kn);
+	if (Z <= 64) launch_ortho_t<BS, 64>(in, out, g, a, x0, x1, st, ch, kn, het);
+	else if (Z <= 128) launch_ortho_t<BS, 128>(in, out, g, a, x0, x1, st, ch, kn, het);
+	else if (Z <= 256) launch_ortho_t<BS, 256>(in, out, g, a, x0, x1, st, ch, kn, het);
+	else if (Z <= 512) launch_ortho_t<BS, 512>(in, out, g, a, x0, x1, st, ch, kn, het);
+	else if constexpr (BS <= 2) launch_ortho_t<BS, 1024>(in, out, g, a, x0, x1, st, ch, kn, het);
 }
 
 bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
-                       hipStream_t st, int chunk, const char** kname, int xb0, int xb1) {
+                       hipStream_t st, int chunk, const char** kname, int xb0, int xb1, const OrthoHet* het) {
 	const char* dummy = nullptr;
 	const char** kn = kname ? kname : &dummy;
 	if (!ortho_supported(g) || x0 < 0 || x1 <= x0 || x1 > g.sizes[0] || chunk < 0) return false;
+	if (het && (!ortho_het_supported(g) || !het->tab || !het->ids || het->n < 1 || het->n > kHetMaxMaterials))
+		return false;
+	if (!het && !a) return false;
 	if (xb1 > xb0 && (xb0 < x1 || xb1 > g.sizes[0])) return false;  // range B after range A
 	for (int r = 0; r < 2; r++) {
 		if (r == 1) {  // no second range in the kernel: a second launch
@@ -286,9 +370,9 @@ bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoA
 			x1 = xb1;
 		}
 		switch (g.bs) {
-		case 1: launch_ortho_bs<1>(in, out, g, a, x0, x1, st, chunk, kn); break;
-		case 2: launch_ortho_bs<2>(in, out, g, a, x0, x1, st, chunk, kn); break;
-		case 3: launch_ortho_bs<3>(in, out, g, a, x0, x1, st, chunk, kn); break;
+		case 1: launch_ortho_bs<1>(in, out, g, a, x0, x1, st, chunk, kn, het); break;
+		case 2: launch_ortho_bs<2>(in, out, g, a, x0, x1, st, chunk, kn, het); break;
+		case 3: launch_ortho_bs<3>(in, out, g, a, x0, x1, st, chunk, kn, het); break;
 		default: return false;
 		}
 	}
@@ -302,5 +386,11 @@ bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoA
 // borderSize-3 windows do not fit them (the instance spilled 79 VGPRs to
 // scratch): borderSize 3 takes rows up to 512 nodes, longer ones the generic stages.
 bool ortho_supported(const Geo& g) { return fused_supported(g) && !(g.bs >= 3 && g.sizes[2] > 512); }
+// The per-node-material instances (ortho_het_built).
+bool ortho_het_supported(const Geo& g) {
+	if (!ortho_supported(g) || g.bs < 1 || g.bs > 3) return false;
+	const int Z = g.sizes[2];
+	return ortho_het_built(g.bs, Z <= 64 ? 64 : Z <= 128 ? 128 : Z <= 256 ? 256 : Z <= 512 ? 512 : 1024);
+}
 #endif
 }  // namespace gcmx

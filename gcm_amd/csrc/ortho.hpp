@@ -41,13 +41,41 @@ bool ortho_axis_extract(int s, const double* U, const double* U1, const double* 
 // rows per block (0 = automatic).  Needs ortho_supported(g), y/z ghosts of both
 // layers zero, x ghost planes of `in` valid.  Two builds, as kernels_xyz.hip's.
 bool ortho_supported(const Geo& g);  // fused_supported(g), and Z <= 512 at borderSize 3
+// Per-node materials for the step (k_step_ortho<..., HET>): per material three
+// OrthoAxis (x, y, z; every pair with floor(q) = 0, its feet on the sides the
+// kernel reads), at most kHetMaxMaterials of them, and the device ids of the
+// inner nodes in linear [x][y][z] order (gcmx_set_material_ids' layout).  Then
+// `a` is unused and may be null.
+struct OrthoHet {
+	const OrthoAxis* tab;  // [n][3], device
+	const uint8_t* ids;
+	int n;
+	int pad_;
+};
+// The HET instances: borderSize 1..3 with rows up to 512 nodes, borderSize 1
+// also up to 1024.  A 1024-thread block leaves 128 VGPRs, within which the
+// per-lane coefficients do not fit beside the borderSize-2 windows (the instance
+// spilled 4 VGPRs, 20 B/lane of scratch; the FMA build 12, 28 B/lane; DESIGN.md
+// §3.10): borderSize >= 2 with rows longer than 512 keeps the generic stages.
+__host__ __device__ constexpr bool ortho_het_built(int bs, int zt) {
+	return bs >= 1 && bs <= 3 && zt <= 1024 && !(bs >= 2 && zt > 512);
+}
+bool ortho_het_supported(const Geo& g);  // ortho_supported(g) and the instance is built
+// Minimum waves per SIMD of an instance: 4 (128 VGPRs) at borderSize <= 2, 2 at 3;
+// the HET instances hold per-lane coefficients in VGPRs and take 2 where the
+// block size allows it (one 512-thread block per CU).
+__host__ __device__ constexpr int ortho_min_waves(int bs, int zt, bool het) {
+	return het ? (zt > 512 ? 4 : 2) : (bs >= 3 ? 2 : 4);
+}
 namespace ortho_exact {
 bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
-                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0);
+                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0,
+                       const OrthoHet* het = nullptr);
 }
 namespace ortho_fma {
 bool launch_step_ortho(const double* in, double* out, const Geo& g, const OrthoAxis* a, int x0, int x1,
-                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0);
+                       hipStream_t st, int chunk = 0, const char** kname = nullptr, int xb0 = 0, int xb1 = 0,
+                       const OrthoHet* het = nullptr);
 }
 
 // ----------------------------------------------------------- structure --

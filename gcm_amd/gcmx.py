@@ -269,6 +269,9 @@ class Context:
         _check(lib().gcmx_set_materials(self._ptr, n, _dp(U), _dp(U1), _dp(L)))
 
     def set_material_ids(self, ids_all: Optional[np.ndarray]):
+        """gcmx_set_material_ids: one uint8 per node of the all-nodes array (ghost
+        entries ignored), None for material 0 everywhere.  Up to 32 materials of the
+        isotropic or of the unrotated orthotropic structure keep the one-pass step."""
         if ids_all is None:
             _check(lib().gcmx_set_material_ids(self._ptr, None))
             return

@@ -52,6 +52,18 @@ def orthotropic_elastic_matrices(rho: float, c):
     return U, U1, L
 
 
+def cross_ply(c):
+    """The nine constants (c11, c12, c13, c22, c23, c33, c44, c55, c66) of the same
+    material turned by 90 degrees about z, i.e. the other ply of a 0/90 laminate:
+    x and y change places, so c11 <-> c22, c13 <-> c23 and c44 <-> c55 swap while
+    c12, c33 and c66 stay.  The result is again an unrotated orthotropic medium."""
+    c = [float(v) for v in np.asarray(c, dtype=np.float64).reshape(-1)]
+    if len(c) != 9:
+        raise ValueError("c must hold the nine elastic constants")
+    c11, c12, c13, c22, c23, c33, c44, c55, c66 = c
+    return (c22, c12, c23, c11, c13, c33, c55, c44, c66)
+
+
 def orthotropic_from_isotropic(rho: float, lam: float, mu: float) -> np.ndarray:
     """OrthotropicMaterial(IsotropicMaterial): c11, c12, c13, c22, c23, c33, c44, c55, c66."""
     c = np.zeros(9)

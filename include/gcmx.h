@@ -105,9 +105,12 @@ void        gcmx_destroy(gcmx_ctx* ctx);
  * util/math/GridCharacteristicMethod.hpp:40-52).  n_mat in 1..255.
  * Any matrices run (the generic per-stage kernel).  Two structures are
  * recognised entry by entry and run faster kernels with identical results:
- * the isotropic ElasticModel matrices, and, in 3-D with one material and no
- * per-node ids, the unrotated orthotropic ones (ElasticModel3D.cpp:286-429:
- * three characteristic pairs per axis with L = (-, +), shear pairs first). */
+ * the isotropic ElasticModel matrices, and, in 3-D, the unrotated orthotropic
+ * ones (ElasticModel3D.cpp:286-429: three characteristic pairs per axis with
+ * L = (-, +), shear pairs first): one material without per-node ids, or, with
+ * per-node ids, 1..32 materials every one of which has that structure (a set
+ * mixing isotropic-pattern and orthotropic materials counts as general).  The
+ * recognition is redone by gcmx_set_material_ids, so the call order is free. */
 gcmx_status gcmx_set_materials(gcmx_ctx* ctx, int n_mat, const double* U,
                                const double* U1, const double* L);
 /* Structure recognised in the matrices of the last gcmx_set_materials:
@@ -116,7 +119,9 @@ int         gcmx_matrix_structure(gcmx_ctx* ctx);
 /* One byte per node of the all-nodes array (getIndex order); NULL means every
  * node uses material 0.  Ghost entries are ignored.  With per-node ids the 3-D
  * step runs in one pass for up to 32 materials (their tables held in LDS, and
- * floor(q) = 0 with equal axes per material); more take the per-stage path. */
+ * floor(q) = 0 with equal axes per material); more take the per-stage path.
+ * Orthotropic materials likewise (k_step_ortho<..., HET>: up to 32, floor(q) = 0
+ * for every pair of every axis of every material, the axes may differ). */
 gcmx_status gcmx_set_material_ids(gcmx_ctx* ctx, const uint8_t* ids_all_nodes);
 
 /* Whole current time layer, host <-> device (DefaultMesh::pdeVariables). */
@@ -147,7 +152,11 @@ gcmx_status gcmx_stage(gcmx_ctx* ctx, int axis, double tau);
  * <= 3, 2 * borderSize <= Z <= 1024 (512 at borderSize 3), no ghost was ever written (border fills,
  * face conditions, contact copies) and the path is AUTO or FUSED; otherwise,
  * and in gcmx_stage, gcmx_step_faces and gcmx_step_face_map, the generic
- * per-stage kernel.  gcmx_step_ode then scales in a separate pass. */
+ * per-stage kernel.  gcmx_step_ode then scales in a separate pass.  With
+ * per-node ids (1..32 orthotropic materials) the same one-pass step takes each
+ * node's own tables under the same conditions when, for this tau, floor(q) = 0
+ * for every material, and Z <= 512 (1024 at borderSize 1); any other tau or
+ * size runs the generic per-stage kernel with identical results. */
 gcmx_status gcmx_step(gcmx_ctx* ctx, double tau);
 gcmx_status gcmx_set_kernel_path(gcmx_ctx* ctx, gcmx_path path);
 /* Step schedule of the fused path and the fused kernel's y rows per block
