@@ -274,11 +274,13 @@ void drain_timings(gcmx_ctx* c) {
 long long round_up(long long v, long long m) { return (v + m - 1) / m * m; }
 
 // GCMX_ROW_PAD and friends (gcmx_create): a non-negative element count rounded
-// up to `align`; 0 when unset.
+// up to `align`; 0 when unset.  An odd count is taken as given: it leaves the
+// rows or planes starting at odd elements, the layout on which the one-pass
+// step must fall back to 8-byte accesses (wide_layout_ok).
 static long long layout_pad(const char* name, long long align) {
 	const char* e = std::getenv(name);
 	const long long v = (e && *e) ? std::atoll(e) : 0;
-	return v > 0 ? round_up(v, align) : 0;
+	return v <= 0 ? 0 : (v & 1) ? v : round_up(v, align);
 }
 
 // Element offset (device layout) of node `it` (multi-index incl. ghosts).

@@ -289,4 +289,38 @@ __device__ __forceinline__ void st_nt_b(const PlanesW& p, int j, unsigned boff, 
 	__builtin_nontemporal_store(v, reinterpret_cast<gptr>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff));
 }
 
+// 16-byte forms (`global_load_dwordx4` / `global_store_dwordx4`): two adjacent
+// doubles of one row; `boff` must be a multiple of 16 from a 16-byte-aligned base.
+typedef double dpair __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ dpair ld2_b(const Planes& p, int j, unsigned boff) {
+	typedef const __attribute__((address_space(1))) char* gcb;
+	typedef const __attribute__((address_space(1))) dpair* gcp2;
+	return *reinterpret_cast<gcp2>(reinterpret_cast<gcb>(p.b[j]) + (unsigned long long)boff);
+}
+__device__ __forceinline__ dpair ld2_nt_b(const Planes& p, int j, unsigned boff) {
+	typedef const __attribute__((address_space(1))) char* gcb;
+	typedef const __attribute__((address_space(1))) dpair* gcp2;
+	return __builtin_nontemporal_load(reinterpret_cast<gcp2>(reinterpret_cast<gcb>(p.b[j]) + (unsigned long long)boff));
+}
+__device__ __forceinline__ void st2_b(const PlanesW& p, int j, unsigned boff, dpair v) {
+	typedef __attribute__((address_space(1))) char* gb;
+	typedef __attribute__((address_space(1))) dpair* gp2;
+	*reinterpret_cast<gp2>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff) = v;
+}
+__device__ __forceinline__ void st2_nt_b(const PlanesW& p, int j, unsigned boff, dpair v) {
+	typedef __attribute__((address_space(1))) char* gb;
+	typedef __attribute__((address_space(1))) dpair* gp2;
+	__builtin_nontemporal_store(v, reinterpret_cast<gp2>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff));
+}
+// Half-wave exchange (two v_permlane32_swap): lanes 32..63 of `a` trade places
+// with lanes 0..31 of `b`.  Every lane of the wave must be active.
+__device__ __forceinline__ void half_swap(double& a, double& b) {
+	typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+	const u32x2 x = __builtin_bit_cast(u32x2, a), y = __builtin_bit_cast(u32x2, b);
+	const u32x2 lo = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false);
+	const u32x2 hi = __builtin_amdgcn_permlane32_swap(x.y, y.y, false, false);
+	a = __builtin_bit_cast(double, u32x2{lo.x, hi.x});
+	b = __builtin_bit_cast(double, u32x2{lo.y, hi.y});
+}
+
 }  // namespace gcmx

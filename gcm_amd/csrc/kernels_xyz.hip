@@ -348,6 +348,9 @@ __device__ unsigned g_tx2_hw[kBlkMax];                   // HW_ID of the block's
 #define GCMX_ZS_PAIRS_FIRST 1  // an XCD's concurrent blocks then cover twice the consecutive pairs: 1024^3 -1.2 % (profiles/r6/n)
 #endif
 
+#ifndef GCMX_TX2_WIDE  // 16-byte global accesses on z-paired half-waves (0: every launch keeps the 8-byte path)
+#define GCMX_TX2_WIDE 1
+#endif
 #ifndef GCMX_TX2_UNROLL  // timing knob: row-loop unroll (5 = the window period: no window moves)
 #define GCMX_TX2_UNROLL 1
 #endif
@@ -438,7 +441,7 @@ __host__ __device__ constexpr int wcomp(unsigned mask, int q) {
 // (Handing the cut lanes' Y results over through memory instead cost 25 %: those
 // lanes' extra stores sit in the vmcnt queue the row-ahead loads are waited on
 // with, profiles/r6/h.)
-template <int BS, int ZT, bool KF0, bool UNI, bool FACES, bool HET, bool ZS = false>
+template <int BS, int ZT, bool KF0, bool UNI, bool FACES, bool HET, bool ZS = false, bool WD = false>
 __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
     const double* __restrict__ in, double* __restrict__ outl, Geo g, IsoAxis AX, IsoAxis AY_,
     IsoAxis AZ_, int x0, int chunk, int nplanes, int xb0, int nplanesb, FaceBC fb,
@@ -466,8 +469,21 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	// barrier: the waves of a block drift apart and overlap their memory phases).
 	constexpr bool NB = UNI && GCMX_TX2_NB;
 	constexpr int NW = ZT / 64;
-	constexpr int RW = 64 + 2 * BS;
 	static_assert(!NB || ZT % 64 == 0, "NB needs whole waves");
+	// WIDE (launches whose every plane, row and part starts 16-byte aligned,
+	// tx2_wide_ok): lane l < 32 of a wave owns column 2l of the wave's 64-column
+	// block and lane l + 32 column 2l + 1, so one 16-byte access of lane l covers
+	// the columns of lanes l and l + 32.  A load brings those two columns of ONE
+	// plane -- the lower half-wave addresses plane a, the upper half plane b --
+	// and half_swap turns the two halves' pairs into every lane's own column of
+	// planes a and b; stores run the same exchange backwards.  `z`, `ln`, `wv`
+	// keep their meaning (the lane's column); only the LDS slots are by lane.
+	constexpr bool WIDE = WD && NB && GCMX_TX2_WIDE && GCMX_TX2_BUF;
+	static_assert(!WD || WIDE, "wide instance launched without its path compiled in");
+	// WIDE: a wave's region holds its even columns -2 .. 64 in slots 0 .. 33 and
+	// its odd columns -1 .. 65 in slots 34 .. 67 (each half-wave reads and writes
+	// 32 consecutive slots: no bank conflicts, as 64 consecutive ones by z)
+	constexpr int RW = WIDE ? 68 : 64 + 2 * BS;
 	constexpr bool ZS2 = GCMX_TX2_ZS2 < 0 ? !NB : GCMX_TX2_ZS2 != 0;
 	__shared__ double zl[NB ? 1 : 2][NB ? 1 : NWZ][NB ? 1 : LW];  // Y results of both nodes (Z stage input)
 	__shared__ double rg[NB ? NW : 1][NB ? 2 : 1][NB ? NWZ : 1][NB ? RW : 1];
@@ -488,10 +504,11 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	const int z = [] {
 		int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 		if constexpr (ZT == 512) w = w < 4 ? 2 * w : 2 * (w - 4) + 1;
-		return w * 64 + (int)(threadIdx.x & 63);
+		const int l = (int)(threadIdx.x & 63);
+		return w * 64 + (WIDE ? ((l & 31) << 1) | (l >> 5) : l);
 	}();
 #else
-	const int z = threadIdx.x;
+	const int z = WIDE ? (int)((threadIdx.x & ~63u) | ((threadIdx.x & 31u) << 1) | ((threadIdx.x >> 5) & 1u)) : (int)threadIdx.x;
 #endif
 #if GCMX_TX2_BLKT
 	const unsigned long long blk_t0_ = __builtin_amdgcn_s_memrealtime();
@@ -593,6 +610,25 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		if constexpr (GCMX_TX2_STNT) st_nt_b(out_p, c, o, v);
 		else st_b(out_p, c, o, v);
 	};
+	// WIDE accessors.  ldw(j, ka, kb, r): the lane's 16 bytes (columns 2l, 2l + 1 of
+	// its wave's block) of component j, row r, of window plane ka (lower half-wave)
+	// or kb (upper half), clamped like ldx's; half_swap(v.x, v.y) after the wait
+	// makes them the lane's own column of planes ka and kb.  stw: the reverse, node
+	// x from the lower half-wave and node x + 1 from the upper.
+	const bool hsel = (threadIdx.x & 32u) != 0;  // upper half-wave
+	const unsigned lw = (zpart + (unsigned)(z & ~63) + 2u * (threadIdx.x & 31u)) * 8u;
+	auto ldw = [&](int j, int ka, int kb, int r, bool nt) {
+		auto cl_ = [&](int k) { return (k == WX - 1 && !two) ? 2 * BS : (k == 0 && !one) ? 1 : k; };
+		const unsigned pa = (pxm + (unsigned)cl_(ka) * stx) * 8u, pb = (pxm + (unsigned)cl_(kb) * stx) * 8u;
+		const unsigned o = opaque_u32(lw + (hsel ? pb : pa) + (unsigned)r * sty * 8u);
+		return nt ? ld2_nt_b(src, j, o) : ld2_b(src, j, o);
+	};
+	auto stw = [&](int c, int y, double v0, double v1) {
+		const unsigned o = opaque_u32(lw + (plane + (hsel ? stx : 0u) + (unsigned)y * sty) * 8u);
+		const dpair v = {v0, v1};
+		if constexpr (GCMX_TX2_STNT) st2_nt_b(out_p, c, o, v);
+		else st2_b(out_p, c, o, v);
+	};
 #else
 	const unsigned base = plane + zc;
 	const Planes src(in + pbase, g.cs);
@@ -653,9 +689,26 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	const int wv = z >> 6, ln = z & 63;  // wave in block, lane
 	// ZS: lanes whose Z stage needs the neighbouring part (k_zseam stores them)
 	const bool seam_own = ZS && ((zp > 0 && z < BS) || (zp < nz - 1 && z >= ZT - BS));
+	// NB: slot of column c (-BS .. 63 + BS of the wave's block) in the wave's region
+	auto rs = [](int c) { return WIDE ? (c >> 1) + ((c & 1) ? 35 : 1) : BS + c; };
+	// the lane's own slot and its z + 1 neighbour's: the Z stage's neighbours at
+	// distance o sit at constant offsets from one of the two (WIDE: odd distances
+	// in the other parity's run, even ones in the lane's own)
+	const int rs0 = rs(ln), rs1 = rs(ln + 1);
+	auto rso = [&](int o) { return !WIDE ? rs0 + o : (o & 1) ? rs1 + ((o - 1) >> 1) : rs0 + (o >> 1); };
+	// WIDE: the lane's 16-byte store covers columns cb, cb + 1 of its part; it is
+	// left out only where k_zseam writes both (a part's cut lanes still compute;
+	// with BS = 1 the pair at a cut holds one cut column, stored here and then
+	// overwritten by k_zseam, which runs after this launch on the same stream)
+	const bool seam_pair = [&] {
+		const int cb = (z & ~63) + 2 * (int)(threadIdx.x & 31u);
+		auto sc = [&](int c) { return (zp > 0 && c < BS) || (zp < nz - 1 && c >= ZT - BS); };
+		return ZS && sc(cb) && sc(cb + 1);
+	}();
+	const int ci = WIDE ? (int)threadIdx.x : z;  // the lane's slot in the `cl` ring (read back by itself only)
 	if constexpr (NB) {  // zero halos (z ghosts stay zero without a z face); counters
 		if (ln < BS || ln >= 64 - BS) {
-			const int hs = ln < BS ? ln : ln + 2 * BS;
+			const int hs = rs(ln < BS ? ln - BS : ln + BS);
 #pragma unroll
 			for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -674,10 +727,34 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	typedef double PairWin[2][WX];  // [vel/sig][plane]
 	auto pair_load = [&](auto PC, PairWin& w, int r) {
 		constexpr int P = decltype(PC)::value;
+		if constexpr (WIDE) {  // raw half-wave pairs: pair_fix before use
+#if GCMX_TX2_BUF
+#pragma unroll
+			for (int m = 0; m < WX / 2; m++) {
+				const dpair a = ldw(pair_vel(0, P), 2 * m, 2 * m + 1, r, false);
+				const dpair b = ldw(pair_sig(0, P), 2 * m, 2 * m + 1, r, false);
+				w[0][2 * m] = a.x, w[0][2 * m + 1] = a.y;
+				w[1][2 * m] = b.x, w[1][2 * m + 1] = b.y;
+			}
+#endif
+			return;
+		}
 #pragma unroll
 		for (int k = 0; k < WX; k++) {
 			w[0][k] = ldx(pair_vel(0, P), k, r);
 			w[1][k] = ldx(pair_sig(0, P), k, r);
+		}
+	};
+	// WIDE: a loaded pair window, once its loads have landed, into the lane's own column
+	auto pair_fix = [&](const PairWin& w, PairWin& u) {
+#pragma unroll
+		for (int v = 0; v < 2; v++) {
+#pragma unroll
+			for (int k = 0; k < WX; k++) u[v][k] = w[v][k];
+			if constexpr (WIDE) {
+#pragma unroll
+				for (int m = 0; m < WX / 2; m++) half_swap(u[v][2 * m], u[v][2 * m + 1]);
+			}
 		}
 	};
 	// Rows 2P, 2P+1 of r = diag(U * V) for both nodes; A0 / A1: the nodes' tables
@@ -744,6 +821,17 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		PairWin a, b;
 	};
 	auto cv_load = [&](double (&cv)[2][9], int r) {
+		if constexpr (WIDE) {  // the own planes as one pair (raw: half_swap in x_compute)
+#if GCMX_TX2_BUF
+#pragma unroll
+			for (int j = 0; j < 9; j++)
+				if ((CMX >> j) & 1u) {
+					const dpair v = ldw(j, BS, BS + 1, r, GCMX_TX2_NTLOAD != 0);
+					cv[0][j] = v.x, cv[1][j] = v.y;
+				}
+#endif
+			return;
+		}
 #pragma unroll
 		for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -763,23 +851,33 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		const int rr_ = r < 0 ? 0 : (r < Y ? r : Y - 1);
 		return mat[((size_t)xx * Y + rr_) * Z + z];
 	};
-	auto x_compute = [&](const XPre& pre, const PairWin& wc, const double (&cv)[2][9], double (&xr)[2][9],
+	auto x_compute = [&](const XPre& pre, const PairWin& wc_, const double (&cv_)[2][9], double (&xr)[2][9],
 	                     const IsoAxis& A0, const IsoAxis& A1, bool same) {
-		double rr[2][9], n0[2][9];
-		pair_rows(P0{}, pre.a, rr, A0, A1, same);
-		pair_rows(P1{}, pre.b, rr, A0, A1, same);
+		double rr[2][9], n0[2][9], cv[2][9];
+		PairWin pa, pb, wc;
+		pair_fix(pre.a, pa);
+		pair_rows(P0{}, pa, rr, A0, A1, same);
+		pair_fix(pre.b, pb);
+		pair_rows(P1{}, pb, rr, A0, A1, same);
 		sched_fence();
+		pair_fix(wc_, wc);
 		pair_rows(P2{}, wc, rr, A0, A1, same);
 #pragma unroll
 		for (int t = 0; t < 2; t++) {
-			n0[t][pair_vel(0, 0)] = pre.a[0][t + BS];
-			n0[t][pair_sig(0, 0)] = pre.a[1][t + BS];
-			n0[t][pair_vel(0, 1)] = pre.b[0][t + BS];
-			n0[t][pair_sig(0, 1)] = pre.b[1][t + BS];
+			n0[t][pair_vel(0, 0)] = pa[0][t + BS];
+			n0[t][pair_sig(0, 0)] = pa[1][t + BS];
+			n0[t][pair_vel(0, 1)] = pb[0][t + BS];
+			n0[t][pair_sig(0, 1)] = pb[1][t + BS];
 			n0[t][pair_vel(0, 2)] = wc[0][t + BS];
 			n0[t][pair_sig(0, 2)] = wc[1][t + BS];
 		}
 		sched_fence();
+#pragma unroll
+		for (int j = 0; j < 9; j++)
+			if ((CMX >> j) & 1u) {
+				cv[0][j] = cv_[0][j], cv[1][j] = cv_[1][j];
+				if constexpr (WIDE) half_swap(cv[0][j], cv[1][j]);
+			}
 #pragma unroll
 		for (int t = 0; t < 2; t++) {
 			const IsoAxis& A = t ? A1 : A0;
@@ -837,7 +935,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	constexpr int S = REV ? -1 : 1;
 	// node-only Y components: ring slot of row r; per-lane pointer with the
 	// (node, component) part as a constant LDS offset
-	auto cl_at = [&](int r) { return &cl[(r + 2 * BS + 2) % (BS + 1)][0][0][z]; };
+	auto cl_at = [&](int r) { return &cl[(r + 2 * BS + 2) % (BS + 1)][0][0][ci]; };
 	// row r's X result enters window slot `slot`; its node-only components go to the ring
 	auto push = [&](const double (&xr)[2][9], int slot, int r) {
 		double* cp = cl_at(r);
@@ -962,13 +1060,13 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 				for (int j = 0; j < 9; j++)
 					if ((WMZ >> j) & 1u) {
 						const int q = wslot(WMZ, j);
-						rg[wv][t][q][BS + ln] = yv[t][j];
+						rg[wv][t][q][rs0] = yv[t][j];
 						if (edge) egp[(t * NWZ + q) * BS] = yv[t][j];
 					}
 			if constexpr (FACES)  // z ghosts: wave 0's left halo, the last wave's right halo
 				z_ghosts(y, yv, [&](int side, int t, int q, double v) {
-					if (side == 0) rg[0][t][q][BS - z] = v;
-					else rg[NW - 1][t][q][BS + 2 * ((ZS ? ZT : Z) - 1) - z - 64 * (NW - 1)] = v;
+					if (side == 0) rg[0][t][q][rs(-z)] = v;
+					else rg[NW - 1][t][q][rs(2 * ((ZS ? ZT : Z) - 1) - z - 64 * (NW - 1))] = v;
 				});
 			// edges in LDS before the counter says so (LDS only: global memory keeps flowing)
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1012,25 +1110,25 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 #pragma unroll
 				for (int t = 0; t < 2; t++)
 #pragma unroll
-					for (int q = 0; q < NWZ; q++) rg[wv][t][q][ln] = eg[es][wv - 1][1][t][q][ln];
+					for (int q = 0; q < NWZ; q++) rg[wv][t][q][rs(ln - BS)] = eg[es][wv - 1][1][t][q][ln];
 			}
 			if (ln >= 64 - BS && wv < NW - 1) {
 #pragma unroll
 				for (int t = 0; t < 2; t++)
 #pragma unroll
-					for (int q = 0; q < NWZ; q++) rg[wv][t][q][ln + 2 * BS] = eg[es][wv + 1][0][t][q][ln - (64 - BS)];
+					for (int q = 0; q < NWZ; q++) rg[wv][t][q][rs(ln + BS)] = eg[es][wv + 1][0][t][q][ln - (64 - BS)];
 			}
 			asm volatile("" ::: "memory");
 		}
 	};
-	// Z stage of node t of row y and its 9 stores
-	auto z_stage_store = [&](int t, int y, const double (&yv)[2][9]) {
-		double zv[9];
+	// Z stage of node t of row y and its 9 stores (WIDE: the results to zv, stored
+	// by z_store_wide once both nodes' are there)
+	auto z_stage_store = [&](int t, int y, const double (&yv)[2][9], double (&zv)[9]) {
 		auto go = [&](const IsoAxis& A) {
 			if constexpr (NB)
 				node_update<2, BS, KF0>(
-				    A, [&](int j, int o) { return rg[wv][t][wslot(WMZ, j)][BS + ln + o]; },
-				    [&](int j) { return ((WMZ >> j) & 1u) ? rg[wv][t][wslot(WMZ, j)][BS + ln] : yv[t][j]; }, zv);
+				    A, [&](int j, int o) { return rg[wv][t][wslot(WMZ, j)][rso(o)]; },
+				    [&](int j) { return ((WMZ >> j) & 1u) ? rg[wv][t][wslot(WMZ, j)][rs0] : yv[t][j]; }, zv);
 			else
 				node_update<2, BS, KF0>(
 				    A, [&](int j, int o) { return zl[t][wslot(WMZ, j)][BS + z + o]; },
@@ -1045,10 +1143,23 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 #pragma unroll
 			for (int c = 3; c < 9; c++) zv[c] = zv[c] * f;
 		}
+		if constexpr (WIDE) return;
 		if ((t == 0 ? one : two) && !(ZS && seam_own)) {
 #pragma unroll
 			for (int c = 0; c < 9; c++) stz(c, t, y, live ? zv[c] : 0.0);
 		}
+	};
+	// WIDE: both nodes' results of row y, 9 16-byte stores: plane x from the lower
+	// half-wave, plane x + 1 from the upper
+	auto z_store_wide = [&](int y, double (&zv)[2][9]) {
+#if GCMX_TX2_BUF
+#pragma unroll
+		for (int c = 0; c < 9; c++) half_swap(zv[0][c], zv[1][c]);
+		if ((hsel ? two : one) && !seam_pair) {
+#pragma unroll
+			for (int c = 0; c < 9; c++) stw(c, y, zv[0][c], zv[1][c]);
+		}
+#endif
 	};
 	// X stage of row y+S*(BS+1) -> window slot W-1 (ghost rows: zero, or a face's mirror)
 	auto x_enter = [&](int y, const XPre& pre, unsigned kn) {
@@ -1078,7 +1189,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		}
 	};
 	auto row = [&](int y, int it) {
-		double yv[2][9];
+		double yv[2][9], zv[2][9];
 		XPre pre;
 		const int rn = clamp_row(y + S * (BS + 1));
 		unsigned kn = 0;  // HET: row rn's materials, one row ahead of its X stage
@@ -1110,8 +1221,9 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 					sched_fence();
 				}
 			}
-			z_stage_store(t, y, yv);
+			z_stage_store(t, y, yv, zv[t]);
 		}
+		if constexpr (WIDE) z_store_wide(y, zv);
 		TX2_T(3);
 		x_enter(y, pre, kn);
 		TX2_T(5);
@@ -1278,13 +1390,22 @@ static bool same_axis(const IsoAxis& p, const IsoAxis& q) {  // bitwise
 }
 
 // The instance a launch runs, as a readable symbol (gcmx_profile_kernel).
-template <int BS, int ZT, bool KF0, bool UNI, bool FACES, bool HET, bool ZS = false>
+// Which access path ran: a UNI instance takes the 16-byte path and keeps its
+// plain name (the one the committed PMC records carry); ", N8" marks a UNI
+// launch that fell back to 8-byte accesses (odd strides, or an instance kept
+// narrow).  The !UNI instances have the 8-byte path only.
+template <int BS, int ZT, bool KF0, bool UNI, bool FACES, bool HET, bool ZS = false, bool WD = false>
 static const char* tx2_name() {
 	static const std::string s = "k_step_tx2<" + std::to_string(BS) + ", " + std::to_string(ZT) + ", " +
 	                             (KF0 ? "KF0" : "!KF0") + ", " + (UNI ? "UNI" : "!UNI") + ", " +
 	                             (FACES ? "FACES" : "!FACES") + (HET ? ", HET" : "") + (ZS ? ", ZS" : "") +
-	                             GCMX_FP_TAG + ">";
+	                             (UNI && !WD ? ", N8" : "") + GCMX_FP_TAG + ">";
 	return s.c_str();
+}
+// The barrier-free instances (UNI) take the wide path when the launch allows it.
+constexpr bool kTx2Wide = (GCMX_TX2_WIDE != 0) & (GCMX_TX2_NB != 0) & (GCMX_TX2_BUF != 0);
+static bool tx2_wide_ok(const Geo& g, const double* in, const double* out) {
+	return kTx2Wide && wide_layout_ok(g) && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
 }
 template <int BS, int ZT, bool KF0, bool UNI>
 static const char* xyz_name() {
@@ -1368,14 +1489,19 @@ static void launch_zs(const double* in, double* out, const Geo& g, const IsoAxis
 	const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * npair * nz);
 	const FaceBC none{};
 	const FaceBC& f = fb ? *fb : none;
-	hipLaunchKernelGGL((k_step_tx2<BS, P, true, true, FACES, false, true>), grid, dim3(P), 0, st, in, out, g, a[0],
-	                   a[1], a[2], x0, chunk, x1 - x0, xb0, nb, f, nullptr, nullptr);
+	auto go = [&](auto WDC) {
+		constexpr bool WD = decltype(WDC)::value;
+		hipLaunchKernelGGL((k_step_tx2<BS, P, true, true, FACES, false, true, WD>), grid, dim3(P), 0, st, in, out, g,
+		                   a[0], a[1], a[2], x0, chunk, x1 - x0, xb0, nb, f, nullptr, nullptr);
+		*kname = tx2_name<BS, P, true, true, FACES, false, true, WD>();
+	};
+	if (tx2_wide_ok(g, in, out)) go(std::integral_constant<bool, kTx2Wide>{});
+	else go(std::false_type{});
 	// the cut columns: 256 / (4 BS) planes per block, 64-row chunks
 	const int np = (x1 - x0) + nb, pb = 256 / (4 * BS), sch = std::min(64, g.sizes[1]);
 	const long long nblk = (long long)((np + pb - 1) / pb) * (nz - 1) * ((g.sizes[1] + sch - 1) / sch);
 	hipLaunchKernelGGL((k_zseam<BS, true, FACES>), dim3((unsigned)nblk), dim3(256), 0, st, in, out, g, a[0], x0,
 	                   x1 - x0, xb0, nb, P, sch, f);
-	*kname = tx2_name<BS, P, true, true, FACES, false, true>();
 }
 
 template <int BS, int ZT>
@@ -1405,17 +1531,31 @@ static void launch_xyz_t(const double* in, double* out, const Geo& g, const IsoA
 				                   nb, f, mt, mi);
 				*kname = name;
 			};
+			// the UNI instances: 16-byte accesses where the layout allows, else the 8-byte path
+			const bool wide = tx2_wide_ok(g, in, out);
+			auto go_uni = [&](auto FC, auto HC) {
+				constexpr bool F = decltype(FC)::value, H = decltype(HC)::value;
+				// per-node materials at borderSize 2 keep the 8-byte path: holding node
+				// 0's results across node 1's Z stage spills there (24-80 B of scratch)
+				// and so do the 256-lane instances: with two blocks per CU the wide path
+				// measured slower (256^3: 4 of 5 alternating pairs, +0.5 .. +4.6 %,
+				// profiles/wide/bench_256_*.jsonl), against -2.3 % at one 512-lane block
+				constexpr bool W = kTx2Wide && !(H && BS == 2) && ZT != 256;
+				if (wide && W) go(k_step_tx2<BS, ZT, true, true, F, H, false, W>,
+				                  tx2_name<BS, ZT, true, true, F, H, false, W>());
+				else go(k_step_tx2<BS, ZT, true, true, F, H>, tx2_name<BS, ZT, true, true, F, H>());
+			};
 			if (het) {  // the caller checked Z == ZT, KF0 and equal axes per material
-				if (fb && fb->on) go(k_step_tx2<BS, ZT, true, true, true, true>, tx2_name<BS, ZT, true, true, true, true>());
-				else go(k_step_tx2<BS, ZT, true, true, false, true>, tx2_name<BS, ZT, true, true, false, true>());
+				if (fb && fb->on) go_uni(std::true_type{}, std::true_type{});
+				else go_uni(std::false_type{}, std::true_type{});
 				return;
 			}
 			if (fb && fb->on) {
-				if (uni) go(k_step_tx2<BS, ZT, true, true, true, false>, tx2_name<BS, ZT, true, true, true, false>());
+				if (uni) go_uni(std::true_type{}, std::false_type{});
 				else if (kf0) go(k_step_tx2<BS, ZT, true, false, true, false>, tx2_name<BS, ZT, true, false, true, false>());
 				else go(k_step_tx2<BS, ZT, false, false, true, false>, tx2_name<BS, ZT, false, false, true, false>());
 			} else {
-				if (uni) go(k_step_tx2<BS, ZT, true, true, false, false>, tx2_name<BS, ZT, true, true, false, false>());
+				if (uni) go_uni(std::false_type{}, std::false_type{});
 				else if (kf0) go(k_step_tx2<BS, ZT, true, false, false, false>, tx2_name<BS, ZT, true, false, false, false>());
 				else go(k_step_tx2<BS, ZT, false, false, false, false>, tx2_name<BS, ZT, false, false, false, false>());
 			}

@@ -94,6 +94,13 @@ bool launch_step2d(const double* cur, double* nxt, const Geo& g, const AxisTable
                    hipStream_t st, const char** kname, const Face2* faces = nullptr);
 bool fast_layout_ok(const Geo& g);     // the per-stage kernels: layer planes < 2^32 bytes
 bool onepass_layout_ok(const Geo& g);  // the one-pass kernels: 32-bit offsets within a block's planes
+// The one-pass step's 16-byte accesses (k_step_tx2's wide path): every plane, row
+// and component plane starts at an even element, so with 16-byte-aligned layers
+// every pair of columns (2l, 2l + 1) is 16-byte aligned.  Otherwise the launch
+// keeps 8-byte accesses.
+inline bool wide_layout_ok(const Geo& g) {
+	return g.D == 3 && ((g.origin | g.stride[0] | g.stride[1] | g.cs) & 1) == 0;
+}
 bool launch_march(const double* cur, double* nxt, const Geo& g, int s, const IsoAxis& A,
                   int x0, int x1, hipStream_t st);
 bool launch_line_z(const double* cur, double* nxt, const Geo& g, const IsoAxis& A, int x0,

@@ -29,6 +29,9 @@ def readable(rocprof_name):
     out = a[:2] + [(f if v == "true" else "!" + f) for f, v in zip(flags, a[2:5])]
     # k_step_tx2's HET and ZS flags appear in the library's name only when set
     out += [f for f, v in zip(["HET", "ZS"], a[5:7]) if v == "true"]
+    # a UNI instance launched on the 8-byte path (8th flag false) is named ", N8"
+    if m.group(1) == "k_step_tx2" and a[3] == "true" and a[7:8] == ["false"]:
+        out.append("N8")
     if "xyz_fma::" in rocprof_name:  # the contracted build (gcmx_set_fp_mode), as the library names it
         out.append("FMA")
     return f"{m.group(1)}<{', '.join(out)}>"
@@ -60,7 +63,7 @@ def main(prof_dir, out, n=512, lib_path="gcm_amd/lib/libgcmx.so", calib_json=Non
     # bench.py's bucket "fused_xyz" is the one-pass step: k_step_tx2 (default) or
     # k_fused_xyz; rows longer than 512 run the z split, k_step_tx2<2, 512, ..., ZS>
     # followed by k_zseam in the same bucket, so their bytes add up
-    zsplit = ("fused_xyz", "k_step_tx2<2, 512, true, true, false, false, true>", "k_zseam<2")
+    zsplit = ("fused_xyz", "k_step_tx2<2, 512, true, true, false, false, true", "k_zseam<2")
     for short, frag, *extra in (("march_x", "k_march<0, 2"), ("fused_yz", f"k_fused_yz<2, {z}"),
                                 ("fused_xyz", f"k_fused_xyz<2, {z}"), ("fused_xyz", f"k_step_tx2<2, {z}"),
                                 *((zsplit,) if n > 512 else ())):

@@ -8,6 +8,7 @@
 //             node: 33 loads) + 9 stores, marching y
 //   xpat_ns : xpat without stores
 //   xtx<TX> : xpat with TX adjacent x planes per thread (loads TX+4 planes)
+//   pw      : xtx<2> through 16-byte accesses on z-paired half-waves (PW_ONLY=1)
 // Build: hipcc --offload-arch=gfx950 -O3 -o tools/xyz_probe tools/xyz_probe.hip
 #include <hip/hip_runtime.h>
 
@@ -154,6 +155,110 @@ __global__ __launch_bounds__(ZT, ZT == 512 ? 2 : 1) void k_probe_tx(const double
 			}
 	}
 	if (!STORE && acc == 1234.5) out[0] = acc;
+}
+
+// The two-plane pattern through 16-byte accesses on z-paired half-waves (the
+// product's wide path, kernels_xyz.hip): lane l < 32 of a wave owns column 2l of
+// the wave's 64 columns, lane l + 32 column 2l + 1.  A window component's six
+// planes come as three 16-byte loads (columns 2l, 2l + 1 of plane 2m in the lower
+// half-wave, of plane 2m + 1 in the upper half) and two v_permlane32_swap per
+// load sort them into the lanes; the node-only components load the own pair the
+// same way; the two nodes' results leave through the reverse exchange, 9 16-byte
+// stores.  WIDE = false: the same kernel with 8-byte accesses (k_probe_tx<2>'s
+// pattern), so that one launch geometry times both.  Trivial arithmetic.
+__device__ __forceinline__ void probe_half_swap(double& a, double& b) {
+	typedef unsigned u2 __attribute__((ext_vector_type(2)));
+	const u2 x = __builtin_bit_cast(u2, a), y = __builtin_bit_cast(u2, b);
+	const u2 lo = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false);
+	const u2 hi = __builtin_amdgcn_permlane32_swap(x.y, y.y, false, false);
+	a = __builtin_bit_cast(double, u2{lo.x, hi.x});
+	b = __builtin_bit_cast(double, u2{lo.y, hi.y});
+}
+template <bool WIDE, int KOPS>
+__global__ __launch_bounds__(512, 2) void k_probe_pw(const double* __restrict__ in, double* __restrict__ out,
+                                                     int chunk) {
+	extern __shared__ double dyn_lds[];
+	if (threadIdx.x == 1023) dyn_lds[0] = 0.0;  // never true: keeps the dynamic LDS request
+	const int T_ = gridDim.x, b = blockIdx.x;
+	const int p = (T_ % 8 == 0) ? (b % 8) * (T_ / 8) + b / 8 : b;
+	const int np = N / 2;
+	const int x = (p % np) * 2, yb = (p / np) * chunk;
+	const int l = threadIdx.x & 31, up = (threadIdx.x >> 5) & 1, wv = threadIdx.x >> 6;
+	// WIDE: the lane's 16 bytes start at column 64 wv + 2 l, in plane (2m + up)
+	const int z = WIDE ? wv * 64 + 2 * l : (int)threadIdx.x;
+	const unsigned base = (unsigned)(ORIGIN + x * STX + z);
+	for (int y = yb; y < yb + chunk; y++) {
+		const unsigned o = base + (unsigned)y * (unsigned)STY;
+		double v[2][9];
+#pragma unroll
+		for (int c = 0; c < 9; c++) {
+			if (c < 6) {
+				double w[6];
+#pragma unroll
+				for (int m = 0; m < 3; m++) {
+					if constexpr (WIDE) {
+						const d2 r = *reinterpret_cast<const d2*>(in + c * CS + (long long)(o + (unsigned)((2 * m + up - BS) * STX)));
+						w[2 * m] = r.x, w[2 * m + 1] = r.y;
+						probe_half_swap(w[2 * m], w[2 * m + 1]);
+					} else {
+						w[2 * m] = in[c * CS + (long long)(o + (unsigned)((2 * m - BS) * STX))];
+						w[2 * m + 1] = in[c * CS + (long long)(o + (unsigned)((2 * m + 1 - BS) * STX))];
+					}
+				}
+#pragma unroll
+				for (int t = 0; t < 2; t++) v[t][c] = w[t] + w[t + 1] + w[t + 2] + w[t + 3] + w[t + 4];
+			} else if constexpr (WIDE) {
+				const d2 r = __builtin_nontemporal_load(reinterpret_cast<const d2*>(in + c * CS + (long long)(o + (unsigned)(up * STX))));
+				v[0][c] = r.x, v[1][c] = r.y;
+				probe_half_swap(v[0][c], v[1][c]);
+			} else {
+#pragma unroll
+				for (int t = 0; t < 2; t++) v[t][c] = __builtin_nontemporal_load(in + c * CS + (long long)(o + (unsigned)(t * STX)));
+			}
+		}
+		if constexpr (KOPS > 0) {
+#pragma unroll
+			for (int t = 0; t < 2; t++)
+#pragma unroll 1
+				for (int k = 0; k < KOPS / 18; k++)
+#pragma unroll
+					for (int c = 0; c < 9; c++) v[t][c] = v[t][c] * 0.999 + 0.001;
+		}
+#pragma unroll
+		for (int c = 0; c < 9; c++) {
+			if constexpr (WIDE) {
+				probe_half_swap(v[0][c], v[1][c]);
+				const d2 r = {v[0][c], v[1][c]};
+				__builtin_nontemporal_store(r, reinterpret_cast<d2*>(out + c * CS + (long long)(o + (unsigned)(up * STX))));
+			} else {
+#pragma unroll
+				for (int t = 0; t < 2; t++)
+					__builtin_nontemporal_store(v[t][c], out + c * CS + (long long)(o + (unsigned)(t * STX)));
+			}
+		}
+	}
+}
+
+template <bool WIDE, int KOPS>
+void pw(const double* in, double* out, int chunk) {
+	const double nodes = (double)N * N * N;
+	const size_t shm = 96 * 1024;  // one block per CU, as the product kernel
+	dim3 grid((N / chunk) * (N / 2));
+	hipEvent_t a, b;
+	CK(hipEventCreate(&a));
+	CK(hipEventCreate(&b));
+	for (int r = 0; r < 11; r++) {
+		if (r == 1) CK(hipEventRecord(a));
+		hipLaunchKernelGGL((k_probe_pw<WIDE, KOPS>), grid, dim3(512), shm, 0, in, out, chunk);
+	}
+	CK(hipEventRecord(b));
+	CK(hipEventSynchronize(b));
+	float ms = 0;
+	CK(hipEventElapsedTime(&ms, a, b));
+	ms /= 10;
+	std::printf("two planes, %s, chunk %3d + %d fp64 ops/node (1 block/CU): %.3f ms (%.0f GB/s)\n",
+	            WIDE ? "16-B paired half-waves" : "8-B lane per column   ", chunk, KOPS, ms, 144.0 * nodes / (ms * 1e6));
+	std::fflush(stdout);
 }
 
 // x-marching: a block is a tile of TYB = TY + 2*BS y rows
@@ -513,6 +618,19 @@ int main() {
 		valu_span(out, cus);
 		copy_span(in, out);
 		valu_span(out, cus);
+		return 0;
+	}
+	if (std::getenv("PW_ONLY")) {  // 16-byte paired half-waves against the shipped 8-byte pattern, alternating
+		copy_span(in, out);
+		for (int r = 0; r < 3; r++) {
+			pw<false, 0>(in, out, 512);
+			pw<true, 0>(in, out, 512);
+			pw<false, 540>(in, out, 512);
+			pw<true, 540>(in, out, 512);
+		}
+		pw<false, 0>(in, out, 128);
+		pw<true, 0>(in, out, 128);
+		copy_span(in, out);
 		return 0;
 	}
 	if (std::getenv("TZ_ONLY")) {  // two planes x two z groups per lane at one wave per SIMD
