@@ -156,7 +156,19 @@ gcmx_status gcmx_stage(gcmx_ctx* ctx, int axis, double tau);
  * per-node ids (1..32 orthotropic materials) the same one-pass step takes each
  * node's own tables under the same conditions when, for this tau, floor(q) = 0
  * for every material, and Z <= 512 (1024 at borderSize 1); any other tau or
- * size runs the generic per-stage kernel with identical results. */
+ * size runs the generic per-stage kernel with identical results.
+ *
+ * Non-finite input: the parity bars hold for finite states.
+ * The limiter is built from v_min_f64 / v_max_f64, which return the operand
+ * that is not NaN, and exact-zero matrix terms are skipped, where the
+ * reference keeps a NaN through its comparisons and forms 0 * NaN.  So inside
+ * the region the reference would fill with NaN (one step: the (2 borderSize +
+ * 1)^dim box around a tainted node) the results of every step and stage call
+ * are unspecified and may be finite -- a NaN in a velocity is gone after one
+ * step; an Inf survives and spreads one node per stage.  Outside that region
+ * the results are the reference's.  No call reports a non-finite state: a
+ * caller that must detect divergence scans a downloaded layer
+ * (gcmx_download) for non-finite or implausibly large values. */
 gcmx_status gcmx_step(gcmx_ctx* ctx, double tau);
 gcmx_status gcmx_set_kernel_path(gcmx_ctx* ctx, gcmx_path path);
 /* Step schedule of the fused path and the fused kernel's y rows per block

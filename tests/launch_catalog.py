@@ -1,0 +1,276 @@
+"""One table of launches: every kernel instance family the step can run, at the
+smallest shapes that reach it.  tests/test_gpu_poison.py, test_gpu_states.py
+and test_gpu_nonfinite.py run all of them; tests/test_states_cpu.py takes the
+material sets.
+
+An entry knows how to build the oracle body (zero state: the caller fills it),
+how both sides advance, what both sides compare (all nodes, or the inner nodes
+where the one-pass face step keeps ghosts on the chip), and the kernel the
+profile must name, so that a case cannot drift onto another instance unnoticed.
+
+Both sides return, per step, the list of states to compare: one for a one-pass
+step, one per stage for the per-stage paths.  Each is a grid [X(, Y(, Z)), M]."""
+import numpy as np
+
+from gcm_amd import PATH_GENERIC, PATH_SPLIT
+from tests.helpers import context_for, oracle_body, random_materials
+from tests.test_gpu_2d import FACE2_CASES, face_body2, faces_at2
+from tests.test_gpu_faces import face_body, faces_at, free
+from tests.test_gpu_ortho import H_A, ortho_body
+from tests.test_gpu_ortho_het import het_body
+from tests.test_gpu_wide_access import MATS, TAU_HET
+
+FREE_ALL = [(0, 0, free(0)), (1, 0, free(1)), (2, 0, free(2))]
+
+
+def courant_tau(b, courant=0.9):
+    return courant * min(b.h[:b.D]) / b.maximal_eigenvalue
+
+
+# ------------------------------------------------------------ material sets --
+# name -> body(bs, sizes) with that set's tables, and its Courant 0.9 time step
+
+def _iso(bs, sizes, start=None):
+    return oracle_body(3, bs, sizes, start=start)
+
+
+def _iso_het(bs, sizes):
+    b = oracle_body(3, bs, sizes, materials=MATS, courant=0.9)
+    random_materials(b, seed=sum(sizes) + bs)
+    return b
+
+
+def _iso2d(bs, sizes):
+    return oracle_body(2, bs, sizes, h=[1.0, 0.5])
+
+
+def _table2d(bs, sizes):
+    """One structural zero of U made non-zero: off the isotropic structure."""
+    b = _iso2d(bs, sizes)
+    for t in b.tables:
+        t[0][0][0, 4] = 1e-3
+    return b
+
+
+MATERIAL_SETS = {
+    "iso": (_iso, lambda b: 0.9),
+    "iso_het": (_iso_het, lambda b: TAU_HET),
+    "ortho": (lambda bs, sizes: ortho_body(bs, sizes), courant_tau),
+    "ortho_het": (lambda bs, sizes: het_body(bs, sizes), courant_tau),
+    "iso2d": (_iso2d, lambda b: 0.45),
+    "table2d": (_table2d, lambda b: 0.45),
+}
+
+
+# ------------------------------------------------------------------ entries --
+
+class Launch:
+    """kind: "step" (gcmx_step, one pass), "faces" (gcmx_step_faces), "stages"
+    (gcmx_stage per axis on a forced path) or "slabs" (an in-process group)."""
+
+    def __init__(self, name, kind, make_body, tau, prefix, marks=(), absent=(), fma_tag=False, compare="all",
+                 conds=None, faces_at=None, path=None, expect_path="fused", slabs=None):
+        self.name, self.kind, self.make_body, self._tau = name, kind, make_body, tau
+        self.prefix = (prefix,) if isinstance(prefix, str) else tuple(prefix)
+        self.marks, self.absent, self.fma_tag = tuple(marks), tuple(absent), fma_tag
+        self.compare = "inner" if kind in ("faces", "slabs") else compare
+        self.conds, self._faces_at, self.slabs = conds, faces_at, slabs
+        self.path, self.expect_path = path, expect_path  # forced kernel path, gcmx_last_step_path
+
+    def __repr__(self):
+        return self.name
+
+    def body(self):
+        return self.make_body()
+
+    def tau(self, body):
+        return self._tau(body) if callable(self._tau) else self._tau
+
+    def grid(self, body, arr):
+        """The compared part of an all-nodes array, as a grid (a copy)."""
+        if self.compare == "inner":
+            return body.inner_view(np.asarray(arr).reshape(body.pde.shape)).copy()
+        return np.asarray(arr).reshape(tuple(body.shape_all) + (body.M,)).copy()
+
+    def node_of(self, body, inner_index):
+        """Index of an inner node in the compared grid."""
+        off = 0 if self.compare == "inner" else body.bs
+        return tuple(int(i) + off for i in inner_index)
+
+    def oracle_step(self, body, t):
+        tau, out = self.tau(body), []
+        for s in range(body.D):
+            if self.kind == "faces":
+                body.apply_border(s, t)
+            body.stage(s, tau)
+            if self.kind == "stages":
+                out.append(self.grid(body, body.pde))
+        if self.kind != "stages":
+            out.append(self.grid(body, body.pde))
+        return out
+
+    def start(self, body, fp):
+        return Run(self, body, fp)
+
+    def check_kernels(self, names, fp_fma):
+        assert names, f"{self.name}: the profile names no kernel"
+        for k in names:
+            assert k.startswith(self.prefix), f"{self.name}: ran {k}, expected {' or '.join(self.prefix)}"
+            for m in self.marks:
+                assert m in k, f"{self.name}: ran {k}, expected an instance with '{m}'"
+            for m in self.absent:
+                assert m not in k, f"{self.name}: ran {k}, expected an instance without '{m}'"
+            if self.fma_tag:
+                assert ("FMA" in k) == fp_fma, f"{self.name}: ran {k} in the {'FMA' if fp_fma else 'exact'} build"
+
+
+class Run:
+    """The GPU side of one entry: its context(s) holding `body`'s state."""
+
+    def __init__(self, launch, body, fp):
+        import gcm_amd
+        self.G, self.launch, self.body, self.tau = gcm_amd, launch, body, launch.tau(body)
+        if launch.kind == "slabs":
+            self.ctxs = self._slabs(body, launch.slabs)
+        else:
+            self.ctxs = [context_for(body, path=launch.path)]
+        for c in self.ctxs:
+            c.fp_mode = fp
+            c.profile(True)
+        self.fp_fma = fp == gcm_amd.FP_FMA
+
+    def _slabs(self, body, widths):
+        """X slabs of `body` as one in-process group, boundary-first schedule; each
+        uploads its own inner planes (x ghosts zero: the exchange fills them)."""
+        G, bs = self.G, body.bs
+        U, U1, L = body.tables[0]
+        whole = body.pde.reshape(tuple(body.shape_all) + (body.M,))
+        out, x0 = [], 0
+        for X in widths:
+            c = G.Context(3, bs, [X] + body.sizes[1:], start=[x0, 0, 0], h=body.h[:3])
+            c.set_materials(U[None], U1[None], L[None])
+            part = np.zeros((X + 2 * bs,) + whole.shape[1:])
+            part[bs:-bs] = whole[bs + x0:bs + x0 + X]
+            c.upload(part)
+            c.set_schedule(G.SCHED_BFIRST)
+            out.append(c)
+            x0 += X
+        G.comm_init_local(out)
+        return out
+
+    def result(self):
+        L, b = self.launch, self.body
+        if L.kind != "slabs":
+            return L.grid(b, self.ctxs[0].download())
+        bs = b.bs
+        parts = [c.download().reshape(tuple(c.shape_all) + (c.M,))[bs:-bs, bs:-bs, bs:-bs] for c in self.ctxs]
+        return np.concatenate(parts, axis=0)
+
+    def step(self, t):
+        L, c = self.launch, self.ctxs[0]
+        if L.kind == "stages":
+            out = []
+            for s in range(self.body.D):
+                c.stage(s, self.tau)
+                assert c.last_path == L.expect_path, f"{L.name}: stage {s} ran {c.last_path}"
+                out.append(self.result())
+            return out
+        if L.kind == "slabs":
+            self.G.local_group_steps(self.ctxs, self.tau, 1)
+        elif L.kind == "faces":
+            c.step_faces(self.tau, L._faces_at(L.conds, t))
+        else:
+            c.step(self.tau)
+        for x in self.ctxs:
+            assert x.last_path == L.expect_path, f"{L.name}: ran {x.last_path}"
+        return [self.result()]
+
+    def kernels(self):
+        """The step kernels the profile names (helper buckets -- face fills, halo
+        copies -- carry no kernel name)."""
+        return [v["kernel"] for c in self.ctxs for v in c.profile_read().values() if v["launches"] > 0 and v["kernel"]]
+
+    def check_kernels(self):
+        names = self.kernels()
+        self.launch.check_kernels(names, self.fp_fma)
+        return names
+
+    def close(self):
+        for c in self.ctxs:
+            c.close()
+
+
+def _tx2(name, bs, sizes, path, start=None, **kw):
+    """path: "wide" (16-byte accesses), "n8" (a UNI launch on the 8-byte path) or
+    "!uni" (idle lanes: the 8-byte instances)."""
+    marks = {"wide": (", UNI",), "n8": (", UNI", ", N8"), "!uni": ("!UNI",)}[path]
+    absent = {"wide": (", N8",), "n8": (), "!uni": ()}[path]
+    return Launch(name, "step", lambda: _iso(bs, sizes, start), 0.9, f"k_step_tx2<{bs}, ", marks + kw.pop("marks", ()),
+                  absent, fma_tag=True, **kw)
+
+
+def _het(name, bs, sizes, path):
+    marks = {"wide": (", UNI", ", HET"), "n8": (", UNI", ", HET", ", N8")}[path]
+    return Launch(name, "step", lambda: _iso_het(bs, sizes), TAU_HET, f"k_step_tx2<{bs}, ", marks,
+                  (", N8",) if path == "wide" else (), fma_tag=True)
+
+
+def _stages(name, sizes, path_name):
+    path = {"split": PATH_SPLIT, "generic": PATH_GENERIC}[path_name]
+    prefix = {"split": ("k_march<", "k_line_z"), "generic": ("k_stage_generic",)}[path_name]
+    return Launch(name, "stages", lambda: _iso(2, sizes), 0.9, prefix, path=path, expect_path=path_name)
+
+
+def _ortho(name, bs, sizes, h=H_A, tau=courant_tau, marks=(", KF0",)):
+    return Launch(name, "step", lambda: ortho_body(bs, sizes, h=h), tau, f"k_step_ortho<{bs}, ", marks,
+                  (", HET",), fma_tag=True)
+
+
+# Face entries take free surfaces (every prescribed value 0): the step stays
+# linear and homogeneous, which the impulse footprints and the power-of-two
+# scaling of tests/test_gpu_states.py rest on.
+def _face2d():
+    bs, sizes, conds, courant, path = FACE2_CASES["free_all"]
+    assert path == "fused"
+    return Launch("2d-faces-free4-30x70", "faces", lambda: face_body2(bs, sizes, conds), courant, "k_step2d_iso<2, ",
+                  (", FACES",), conds=conds, faces_at=faces_at2)
+
+
+CATALOG = [
+    # ---- k_step_tx2
+    _tx2("tx2-wide-bs2-4x5x64", 2, [4, 5, 64], "wide"),
+    _tx2("tx2-wide-bs2-3x6x128", 2, [3, 6, 128], "wide"),
+    _tx2("tx2-wide-bs1-4x5x64", 1, [4, 5, 64], "wide"),
+    _tx2("tx2-wide-start1-bs2-4x5x64", 2, [4, 5, 64], "wide", start=[1, 0, 0]),
+    _tx2("tx2-n8-bs2-3x6x256", 2, [3, 6, 256], "n8"),
+    _tx2("tx2-!uni-bs2-4x6x40", 2, [4, 6, 40], "!uni"),
+    _tx2("tx2-zs-bs2-4x12x1024", 2, [4, 12, 1024], "wide", marks=(", ZS",)),
+    _het("tx2-het-bs1-5x7x64", 1, [5, 7, 64], "wide"),
+    _het("tx2-het-bs2-4x6x128", 2, [4, 6, 128], "n8"),
+    Launch("tx2-faces-free6-bs2-4x8x64", "faces", lambda: face_body(3, 2, [4, 8, 64], FREE_ALL), 0.9,
+           "k_step_tx2<2, ", (", UNI", ", FACES"), ("!FACES", ", N8"), fma_tag=True, conds=FREE_ALL,
+           faces_at=lambda conds, t: faces_at(3, conds, t)),
+    # floor(q) = 1 on the fast waves: whichever of the two kernels the dispatch
+    # takes (k_step_tx2's !KF0 instance at this border size; see the profile)
+    Launch("courant15-bs2-4x6x64", "step", lambda: _iso(2, [4, 6, 64]), 1.5, ("k_step_tx2<2, ", "k_fused_xyz<2, "),
+           ("!KF0",), fma_tag=True),
+    # ---- other 3-D paths
+    Launch("fused_xyz-bs3-4x7x100", "step", lambda: _iso(3, [4, 7, 100]), 0.9, "k_fused_xyz<3, ", fma_tag=True),
+    _stages("split-bs2-9x4x300", [9, 4, 300], "split"),
+    _stages("generic-bs2-5x6x70", [5, 6, 70], "generic"),
+    _ortho("ortho-bs2-6x9x37", 2, [6, 9, 37]),
+    _ortho("ortho-bs2-4x5x65", 2, [4, 5, 65]),
+    _ortho("ortho-bs3-5x7x20", 3, [5, 7, 20]),
+    _ortho("ortho-!kf0-bs2-6x9x37", 2, [6, 9, 37], h=(1.0, 1.0, 1.0), tau=0.158, marks=("!KF0",)),
+    Launch("ortho-het-bs2-6x9x37", "step", lambda: het_body(2, [6, 9, 37]), courant_tau, "k_step_ortho<2, ",
+           (", KF0", ", HET"), fma_tag=True),
+    Launch("slabs-bfirst-bs2-8+8x6x64", "slabs", lambda: _iso(2, [16, 6, 64]), 0.9, "k_step_tx2<2, ", fma_tag=True,
+           slabs=(8, 8)),
+    # ---- 2-D
+    Launch("2d-iso-bs2-21x70", "step", lambda: _iso2d(2, [21, 70]), 0.45, "k_step2d_iso<2, "),
+    Launch("2d-iso-bs1-130x253", "step", lambda: _iso2d(1, [130, 253]), 0.45, "k_step2d_iso<1, "),
+    Launch("2d-table-bs2-30x300", "step", lambda: _table2d(2, [30, 300]), 0.45, "k_step2d<2, "),
+    _face2d(),
+]
+BY_NAME = {e.name: e for e in CATALOG}
+assert len(BY_NAME) == len(CATALOG)
