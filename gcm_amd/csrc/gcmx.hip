@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "ortho.hpp"
+#include "acoustic.hpp"
 
 using namespace gcmx;
 static_assert(GCMX_MAX_BORDER_Q == kMaxBorderQ, "border quantity limit");
@@ -157,6 +158,10 @@ struct gcmx_ctx {
 	bool ortho_het_ok = false;     // this tau: every material's feet on the sides the kernel reads, floor(q) = 0
 	std::vector<OrthoAxis> ortho_het_h;  // [mat][3]: per-axis values (tau part in build_tables)
 	OrthoAxis* ortho_het_d = nullptr;    // [mat][3] on the device, per tau
+	gcmx_model model = GCMX_MODEL_ELASTIC;  // what the PDE vector holds (gcmx_create_model)
+	bool ac_fast = false;          // acoustic context, one material, no ids, the acoustic structure
+	bool ac_ok = false;            // this tau: each axis's two feet on the sides k_step_acoustic reads, q != 0
+	AcAxis ac[3] = {};             // per-axis values (tau part in build_tables)
 	bool ghosts_touched = false;   // node-list border fills / contact copies / ghost uploads happened
 	bool last_ode_fused = false;   // the last gcmx_step_ode scaled the stresses in the step's epilogue
 	unsigned faces_written = 0;    // faces (bit 2*axis + side) whose ghosts a face fill wrote
@@ -371,6 +376,20 @@ gcmx_status build_tables(gcmx_ctx* c, double tau) {
 				A.kf[p] = t.kf[k];
 				lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
 			}
+		}
+	}
+	if (c->ac_fast) {
+		// rows 0 (L = +c: foot on the -s side) and 1 (+s side) share q; a step that
+		// puts them elsewhere (tau <= 0) or on the node (q = 0) takes the generic stages
+		c->ac_ok = true;
+		for (int s = 0; s < D; s++) {
+			const AxisTable& t = h[s];
+			AcAxis& A = c->ac[s];
+			if (t.kf[0] != t.kf[1] || std::memcmp(t.coef[0], t.coef[1], sizeof(t.coef[0])) != 0)
+				return fail(GCMX_ERR_STATE, "inconsistent foot data");
+			if (t.shift[0] != -1 || t.shift[1] != 1 || t.zero_q[0] || t.zero_q[1]) c->ac_ok = false;
+			for (int i = 0; i < 3; i++) A.c[i] = i < bs ? t.coef[0][i] : 0.0;
+			A.kf = t.kf[0];
 		}
 	}
 	if (c->ortho_het) {
@@ -844,11 +863,77 @@ bool gcmx::ortho_axis_extract(int s, const double* U, const double* U1, const do
 	return L[6] == 0.0 && L[7] == 0.0 && L[8] == 0.0;
 }
 
+// The acoustic pattern (acoustic.hpp), entry by entry: rows 0 / 1 of U read the
+// axis velocity with exactly 0.5 and the pressure with exactly opposite finite
+// non-zero coefficients, columns 0 / 1 of U1 hold exactly 1.0 on the axis
+// velocity and opposite values on the pressure, L = (+c, -c, 0...); each zero
+// mode k >= 2 is one entry of magnitude exactly 1.0 on one tangential velocity,
+// the same entry in row k of U and in column k of U1 (either sign: the
+// reference's local basis gives tangents like (0, -1), and the two flips cancel
+// exactly in U1 (U u)), the modes' velocities distinct; every other entry is
+// an exact zero.
+bool gcmx::acoustic_axis_extract(int D, int s, const double* U, const double* U1, const double* L, AcAxis& A) {
+	if (D < 1 || D > 3 || s < 0 || s >= D) return false;
+	const int M = D + 1;
+	if (!(L[0] > 0) || !std::isfinite(L[0]) || !(L[1] == -L[0])) return false;
+	for (int k = 2; k < M; k++)
+		if (L[k] != 0.0) return false;
+	const double u0 = U[0 * M + D], p0 = U1[D * M + 0];
+	if (!std::isfinite(u0) || u0 == 0.0 || !std::isfinite(p0) || p0 == 0.0) return false;
+	int mode_of[3] = {-1, -1, -1};  // tangential velocity -> its zero mode
+	for (int k = 2; k < M; k++) {
+		int t = -1;
+		for (int j = 0; j < D; j++)
+			if (j != s && U[k * M + j] != 0.0) {
+				if (t >= 0) return false;
+				t = j;
+			}
+		if (t < 0 || mode_of[t] >= 0 || std::fabs(U[k * M + t]) != 1.0) return false;
+		mode_of[t] = k;
+	}
+	for (int k = 0; k < M; k++)
+		for (int j = 0; j < M; j++) {
+			double wu = 0.0, wu1 = 0.0;  // the pattern's U(k, j) and U1(j, k)
+			if (k < 2) {
+				if (j == s) {
+					wu = 0.5;
+					wu1 = 1.0;
+				} else if (j == D) {
+					wu = k == 0 ? u0 : -u0;
+					wu1 = k == 0 ? p0 : -p0;
+				}
+			} else if (j < D && mode_of[j] == k) {
+				wu = wu1 = U[k * M + j];
+			}
+			if (U[k * M + j] != wu || U1[j * M + k] != wu1) return false;
+		}
+	A.u0 = u0;
+	A.u1 = U[1 * M + D];
+	A.p0 = p0;
+	A.p1 = U1[D * M + 1];
+	return true;
+}
+
 namespace {
 
 // Fast kernels: 3-D, one material, no per-node ids, isotropic zero pattern.
 void refresh_fast(gcmx_ctx* c) {
 	const int D = c->D, M = c->M;
+	if (c->model == GCMX_MODEL_ACOUSTIC) {
+		// the elastic patterns index 9 (5) columns: none is tried.  One material
+		// without per-node ids of the acoustic pattern: structure 3, and in 3-D the
+		// one-pass step where the layout admits it (effective_path)
+		c->iso_fast = c->iso2_fast = c->iso_het = c->het_ok = false;
+		c->ortho_fast = c->ortho_ok = c->ortho_het = c->ortho_het_ok = false;
+		bool ac = c->mat_d == nullptr && c->n_mat == 1;
+		for (int sx = 0; ac && sx < D; sx++)
+			ac = acoustic_axis_extract(D, sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M],
+			                           &c->L[(size_t)sx * M], c->ac[sx]);
+		c->ac_fast = ac;
+		c->ac_ok = ac;
+		c->tabs_tau = NAN;
+		return;
+	}
 	bool fits = (D == 3) && (c->mat_d == nullptr) && (c->n_mat == 1) && onepass_layout_ok(c->geo);
 	for (int sx = 0; fits && sx < D; sx++)
 		fits = iso_axis_extract(sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M],
@@ -898,7 +983,7 @@ void refresh_fast(gcmx_ctx* c) {
 // the two layers' ghosts agree, whichever one the step leaves the state in),
 // no X-slab exchange, a borderSize it is built for, and no forced per-stage path.
 bool step2d_admissible(const gcmx_ctx* c) {
-	return c->D == 2 && step2d_supported(c->geo) && c->mat_d == nullptr && c->n_mat == 1 && !c->ghosts_touched &&
+	return c->D == 2 && c->model == GCMX_MODEL_ELASTIC && step2d_supported(c->geo) && c->mat_d == nullptr && c->n_mat == 1 && !c->ghosts_touched &&
 	       c->faces_written == 0 && !has_halo(c) && c->path != GCMX_PATH_GENERIC && c->path != GCMX_PATH_SPLIT;
 }
 // The same with whole-face border conditions `on` (bit 2*axis + side): the
@@ -912,6 +997,12 @@ bool step2d_faces_admissible(const gcmx_ctx* c, unsigned on) {
 }
 
 gcmx_path effective_path(gcmx_ctx* c) {
+	if (c->model == GCMX_MODEL_ACOUSTIC) {  // the one-pass acoustic step (3-D) or the generic stages
+		const bool onepass = c->D == 3 && c->ac_fast && c->ac_ok && c->bs <= 3 && acoustic_supported(c->geo) &&
+		                     !c->ghosts_touched && c->faces_written == 0 && !has_halo(c) &&
+		                     (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
+		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
+	}
 	if (c->iso_het) {  // per-node materials: the one-pass step or the generic stages
 		if (c->path == GCMX_PATH_GENERIC || c->path == GCMX_PATH_SPLIT || c->ghosts_touched) return GCMX_PATH_GENERIC;
 		return GCMX_PATH_FUSED;
@@ -941,6 +1032,7 @@ double node_stage_bytes(const gcmx_ctx* c) { return 2.0 * c->M * sizeof(double);
 // PhysicalQuantities code -> component of the D-dimensional PDE vector
 // (VelocitySigmaVariables.cpp:51-66); -1 if absent (PRESSURE: 12, handled apart).
 int quantity_comp(int D, int q) {
+	if (q >= kDirectQ) return q - kDirectQ;  // an acoustic context's pressure (border_q)
 	if (q >= 2 && q <= 4) return (q - 2) < D ? q - 2 : -1;
 	if (q >= 5 && q <= 10) {
 		static const int ii[6] = {0, 0, 0, 1, 1, 2}, jj[6] = {0, 1, 2, 1, 2, 2};
@@ -955,6 +1047,17 @@ gcmx_status border_q(const gcmx_ctx* c, int n_q, const int* qs, const double* va
 	if (n_q < 0 || n_q > kMaxBorderQ || (n_q > 0 && (!qs || !vals)))
 		return fail(GCMX_ERR_INVALID_ARG, "bad border quantities (at most 16)");
 	bq.n = n_q;
+	if (c->model == GCMX_MODEL_ACOUSTIC) {
+		// AcousticVariables::QUANTITIES: Vx..Vz and PRESSURE, which is component D
+		// itself (kDirectQ + D for the kernels: no trace, nothing cleared)
+		for (int k = 0; k < n_q; k++) {
+			const bool vel = qs[k] >= 2 && qs[k] <= 4 && qs[k] - 2 < c->D;
+			if (!vel && qs[k] != 12) return fail(GCMX_ERR_INVALID_ARG, "quantity not in the acoustic PDE vector");
+			bq.q[k] = vel ? qs[k] : kDirectQ + c->D;
+			bq.v[k] = vals[k];
+		}
+		return GCMX_OK;
+	}
 	for (int k = 0; k < n_q; k++) {
 		if (qs[k] != 12 && quantity_comp(c->D, qs[k]) < 0)
 			return fail(GCMX_ERR_INVALID_ARG, "quantity not in this PDE vector");
@@ -977,7 +1080,7 @@ gcmx_status stage_impl(gcmx_ctx* c, int axis, double tau) {
 	const double bytes = node_stage_bytes(c) * (double)g.n_inner;
 	// no per-stage het kernels; the per-stage kernels of the split path are 3-D only
 	const gcmx_path p =
-	    (c->iso_het || c->ortho_fast || c->ortho_het || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC
+	    (c->model == GCMX_MODEL_ACOUSTIC || c->iso_het || c->ortho_fast || c->ortho_het || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC
 	                                                                                          : effective_path(c);
 	bool ok;
 	if (p == GCMX_PATH_GENERIC) {
@@ -1010,6 +1113,11 @@ extern "C" {
 int gcmx_abi_version(void) { return GCMX_ABI_VERSION; }
 const char* gcmx_last_error(void) { return g_last_error.c_str(); }
 int gcmx_pde_size(int dim) { return (dim >= 1 && dim <= 3) ? pde_size(dim) : -1; }
+int gcmx_model_pde_size(gcmx_model model, int dim) {
+	if (dim < 1 || dim > 3) return -1;
+	return model == GCMX_MODEL_ELASTIC ? pde_size(dim) : model == GCMX_MODEL_ACOUSTIC ? dim + 1 : -1;
+}
+gcmx_model gcmx_get_model(const gcmx_ctx* c) { return c ? c->model : GCMX_MODEL_ELASTIC; }
 
 const char* gcmx_status_string(gcmx_status s) {
 	switch (s) {
@@ -1147,8 +1255,13 @@ static long long shuffle_policy_mib(size_t block, bool* contig) {
 }
 
 gcmx_status gcmx_create(const gcmx_grid_desc* d, int device, gcmx_ctx** out) {
+	return gcmx_create_model(d, GCMX_MODEL_ELASTIC, device, out);
+}
+
+gcmx_status gcmx_create_model(const gcmx_grid_desc* d, gcmx_model model, int device, gcmx_ctx** out) {
 	if (!d || !out) return fail(GCMX_ERR_INVALID_ARG, "null argument");
 	*out = nullptr;
+	if (model != GCMX_MODEL_ELASTIC && model != GCMX_MODEL_ACOUSTIC) return fail(GCMX_ERR_INVALID_ARG, "unknown model");
 	if (d->dim < 1 || d->dim > 3) return fail(GCMX_ERR_INVALID_ARG, "dim must be 1..3");
 	// CubicGrid ctor: assert_gt(borderSize, 0), sizes >= borderSize, h > 0 (CubicGrid.hpp:193-199)
 	if (d->border_size <= 0 || d->border_size > kMaxBs)
@@ -1171,7 +1284,8 @@ gcmx_status gcmx_create(const gcmx_grid_desc* d, int device, gcmx_ctx** out) {
 	if (const char* e = std::getenv("GCMX_FP")) c->fp_mode = std::strcmp(e, "exact") == 0 ? GCMX_FP_EXACT : GCMX_FP_FMA;
 	c->desc = *d;
 	c->D = d->dim;
-	c->M = pde_size(d->dim);
+	c->model = model;
+	c->M = gcmx_model_pde_size(model, d->dim);
 	c->bs = d->border_size;
 	Geo& g = c->geo;
 	g.D = c->D;
@@ -1608,6 +1722,8 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 	const bool halo = has_halo(c);
 	auto xyz = [&](const char* name, int x0, int x1, hipStream_t st, int rows, int xb0 = 0, int xb1 = 0) {
 		Timed t(c, name, plane_bytes * ((x1 - x0) + (xb1 - xb0)), st);
+		if (c->model == GCMX_MODEL_ACOUSTIC)  // effective_path admitted it: no face conditions, no halo, one range
+			return fb == nullptr && xb1 <= xb0 && launch_step_acoustic(c->cur, c->nxt, g, c->ac, x0, x1, st, rows, &t.kname);
 		if (c->ortho_fast || c->ortho_het) {  // effective_path admitted it: no face conditions, no folded ODE
 			auto launch_o = c->fp_mode == GCMX_FP_EXACT ? ortho_exact::launch_step_ortho : ortho_fma::launch_step_ortho;
 			const OrthoHet ohet{c->ortho_het_d, c->mat_d, c->n_mat, 0};  // this context's own inner nodes' ids
@@ -1620,7 +1736,9 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 		              xb0, xb1);
 	};
 	const gcmx_schedule sched =
-	    c->sched == GCMX_SCHED_AUTO ? (halo ? GCMX_SCHED_BFIRST : GCMX_SCHED_SINGLE) : c->sched;
+	    c->model == GCMX_MODEL_ACOUSTIC ? GCMX_SCHED_SINGLE  // no X slabs: nothing to schedule around
+	    : c->sched == GCMX_SCHED_AUTO   ? (halo ? GCMX_SCHED_BFIRST : GCMX_SCHED_SINGLE)
+	                                    : c->sched;
 	bool ok = true;
 	// boundary rows per block: 16 beside the interior (XSLAB), 4 alone on the
 	// GPU (BFIRST: 2 x 128 blocks for a 512^2 face); GCMX_BOUNDARY_ROWS
@@ -1835,6 +1953,8 @@ gcmx_status gcmx_step_ode(gcmx_ctx* c, double tau, const gcmx_face* faces, const
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
 	if (!std::isfinite(tau)) return fail(GCMX_ERR_INVALID_ARG, "non-finite time step");
+	if (c->model == GCMX_MODEL_ACOUSTIC)
+		return fail(GCMX_ERR_UNSUPPORTED, "gcmx_step_ode: the acoustic model has no ODE (AcousticModel::OdeVariables is void)");
 	StepOde ode;
 	if ((s = ode_factors(c, tau, tau0, n_mat, ode)) != GCMX_OK) return s;
 	return faces ? step_faces_impl(c, tau, faces, ode) : step_impl(c, tau, ode);
@@ -1910,7 +2030,7 @@ gcmx_status step_faces_body(gcmx_ctx* c, double tau, const gcmx_face* faces, con
 	// One pass: x faces in memory, y/z faces as FaceBC; the y/z faces must be
 	// free of PRESSURE (its trace needs components the fused ghosts do not form)
 	// and no face may hold ghosts written earlier but not refreshed now.
-	bool fused = D == 3 && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && c->model == GCMX_MODEL_ELASTIC && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	FaceBC fb{};
@@ -2056,7 +2176,7 @@ static gcmx_status step_face_map_body(gcmx_ctx* c, double tau, const gcmx_face_m
 	launch_set_face_tables(m->bq_d, m->fc_d, t, c->stream);
 	HIP_TRY(hipGetLastError());
 	c->last_ode_fused = false;
-	bool fused = D == 3 && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
+	bool fused = D == 3 && c->model == GCMX_MODEL_ELASTIC && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
 	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
 	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
 	for (int f = 2; f < 2 * D && fused; f++)
@@ -2133,6 +2253,7 @@ gcmx_status gcmx_set_kernel_path(gcmx_ctx* c, gcmx_path p) {
 
 int gcmx_matrix_structure(gcmx_ctx* c) {
 	if (!c || c->n_mat <= 0) return 0;
+	if (c->model == GCMX_MODEL_ACOUSTIC) return c->ac_fast ? 3 : 0;
 	return (c->iso_fast || c->iso2_fast || c->iso_het) ? 1 : (c->ortho_fast || c->ortho_het) ? 2 : 0;
 }
 
@@ -2239,6 +2360,8 @@ gcmx_status gcmx_ode_maxwell(gcmx_ctx* c, double tau, const double* tau0, int n_
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
 	if (!std::isfinite(tau)) return fail(GCMX_ERR_INVALID_ARG, "non-finite time step");
+	if (c->model == GCMX_MODEL_ACOUSTIC)
+		return fail(GCMX_ERR_UNSUPPORTED, "gcmx_ode_maxwell: the acoustic model has no ODE (AcousticModel::OdeVariables is void)");
 	StepOde ode;
 	if ((s = ode_factors(c, tau, tau0, n_mat, ode)) != GCMX_OK) return s;
 	return ode_apply(c, ode.f);
@@ -2287,7 +2410,7 @@ gcmx_status gcmx_copy_box(gcmx_ctx* dst, const int dmin[3], const int dmax[3], g
                           const int smin[3]) {
 	gcmx_status s = check_ctx(dst);
 	if (s) return s;
-	if (!src || !dmin || !dmax || !smin || src->D != dst->D || src->M != dst->M ||
+	if (!src || !dmin || !dmax || !smin || src->D != dst->D || src->M != dst->M || src->model != dst->model ||
 	    src->device != dst->device)
 		return fail(GCMX_ERR_INVALID_ARG, "bad copy-box arguments");
 	const int D = dst->D;
@@ -2379,6 +2502,7 @@ gcmx_status gcmx_comm_init_opts(gcmx_ctx* c, const uint8_t id[GCMX_UNIQUE_ID_BYT
                                 int left, int right, const gcmx_comm_options* opt) {
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
+	if (c->model == GCMX_MODEL_ACOUSTIC) return fail(GCMX_ERR_UNSUPPORTED, "X slabs are not built for acoustic contexts");
 	// A neighbour equal to this rank is accepted only in a one-rank communicator
 	// (the self-exchange that runs the RCCL transport on a one-GPU box, gcmx.h).
 	if (!id || nranks < 1 || rank < 0 || rank >= nranks || left >= nranks || right >= nranks ||
@@ -2493,6 +2617,7 @@ gcmx_status gcmx_comm_test_stall(gcmx_ctx* c, int on) {
 gcmx_status gcmx_comm_init_loopback(gcmx_ctx* c, double gbps_per_direction, int blocks) {
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
+	if (c->model == GCMX_MODEL_ACOUSTIC) return fail(GCMX_ERR_UNSUPPORTED, "X slabs are not built for acoustic contexts");
 	if (c->D < 2) return fail(GCMX_ERR_INVALID_ARG, "X-slab halo needs dim >= 2");
 	if (!(gbps_per_direction >= 0) || blocks < 1 || blocks > 1024)
 		return fail(GCMX_ERR_INVALID_ARG, "loopback: rate >= 0 GB/s and 1..1024 blocks expected");
@@ -2586,6 +2711,7 @@ gcmx_status gcmx_comm_init_local(gcmx_ctx* const* ctxs, int n) {
 	for (int i = 0; i < n; i++) {
 		gcmx_ctx* c = ctxs[i];
 		if (!c || c->D < 2) return fail(GCMX_ERR_INVALID_ARG, "bad slab (null or dim < 2)");
+		if (c->model == GCMX_MODEL_ACOUSTIC) return fail(GCMX_ERR_UNSUPPORTED, "X slabs are not built for acoustic contexts");
 		if (c->comm || c->lc) return fail(GCMX_ERR_STATE, "communicator already initialised");
 		for (int j = 0; j < i; j++)
 			if (ctxs[j] == c) return fail(GCMX_ERR_INVALID_ARG, "a context appears twice");

@@ -8,17 +8,19 @@
 // non-zero U entry asks for are interpolated (the per-component interpolation
 // is independent).  Summation order of the remaining terms is the reference's
 // (linal/functions.hpp:254-267, linal/operators.hpp:109-123).
+#include "acoustic.hpp"
 #include "common.hpp"
 #include "launch.hpp"
 
 namespace gcmx {
 
-template <int D, int BS, bool HETERO>
+// M: components of the PDE vector -- pde_size(D) for elastic contexts, D + 1
+// for acoustic ones (Geo::M; the tables are indexed U[k * M + j]).
+template <int D, int M, int BS, bool HETERO>
 __global__ __launch_bounds__(256) void k_stage_generic(const double* __restrict__ cur,
                                                        double* __restrict__ nxt, Geo g, int s,
                                                        const AxisTable* __restrict__ tabs,
                                                        const uint8_t* __restrict__ mat) {
-	constexpr int M = pde_size(D);
 	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= g.n_inner) return;
 	const int z = (int)(i % g.sizes[2]);
@@ -122,7 +124,10 @@ __global__ __launch_bounds__(256) void k_copy_box(double* __restrict__ dst, Geo 
 // cubic::BorderConditions::handleBorderPoint (engine/cubic/BorderConditions.hpp:94-114)
 // for a list of face nodes.  quantity codes: PhysicalQuantities::T.
 __host__ __device__ __forceinline__ int quantity_component(int D, int q) {
-	// Vx..Vz = 2..4 ; Sxx,Sxy,Sxz,Syy,Syz,Szz = 5..10 (VelocitySigmaVariables.cpp:51-66)
+	// Vx..Vz = 2..4 ; Sxx,Sxy,Sxz,Syy,Syz,Szz = 5..10 (VelocitySigmaVariables.cpp:51-66);
+	// kDirectQ + c: component c itself (how the host names an acoustic context's
+	// pressure, AcousticVariables::QUANTITIES: PRESSURE is component D, no trace)
+	if (q >= kDirectQ) return q - kDirectQ;
 	if (q >= 2 && q <= 4) return (q - 2) < D ? q - 2 : -1;
 	if (q >= 5 && q <= 10) {
 		const int ii[6] = {0, 0, 0, 1, 1, 2};
@@ -265,40 +270,44 @@ __global__ __launch_bounds__(64) void k_set_face_tables(BorderQ* __restrict__ bq
 
 // ---------------------------------------------------------------- launchers --
 
-template <int D, int BS>
+template <int D, int M, int BS>
 static void launch_generic_dbs(const double* cur, double* nxt, const Geo& g, int s,
                                const AxisTable* tabs, const uint8_t* mat, hipStream_t st) {
 	const long long blocks = (g.n_inner + 255) / 256;
 	if (mat)
-		hipLaunchKernelGGL((k_stage_generic<D, BS, true>), dim3((unsigned)blocks), dim3(256), 0,
+		hipLaunchKernelGGL((k_stage_generic<D, M, BS, true>), dim3((unsigned)blocks), dim3(256), 0,
 		                   st, cur, nxt, g, s, tabs, mat);
 	else
-		hipLaunchKernelGGL((k_stage_generic<D, BS, false>), dim3((unsigned)blocks), dim3(256),
+		hipLaunchKernelGGL((k_stage_generic<D, M, BS, false>), dim3((unsigned)blocks), dim3(256),
 		                   0, st, cur, nxt, g, s, tabs, mat);
 }
 
-template <int D>
+template <int D, int M>
 static bool launch_generic_d(const double* cur, double* nxt, const Geo& g, int s,
                              const AxisTable* tabs, const uint8_t* mat, hipStream_t st) {
 	switch (g.bs) {
-	case 1: launch_generic_dbs<D, 1>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 2: launch_generic_dbs<D, 2>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 3: launch_generic_dbs<D, 3>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 4: launch_generic_dbs<D, 4>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 5: launch_generic_dbs<D, 5>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 6: launch_generic_dbs<D, 6>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 7: launch_generic_dbs<D, 7>(cur, nxt, g, s, tabs, mat, st); return true;
-	case 8: launch_generic_dbs<D, 8>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 1: launch_generic_dbs<D, M, 1>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 2: launch_generic_dbs<D, M, 2>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 3: launch_generic_dbs<D, M, 3>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 4: launch_generic_dbs<D, M, 4>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 5: launch_generic_dbs<D, M, 5>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 6: launch_generic_dbs<D, M, 6>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 7: launch_generic_dbs<D, M, 7>(cur, nxt, g, s, tabs, mat, st); return true;
+	case 8: launch_generic_dbs<D, M, 8>(cur, nxt, g, s, tabs, mat, st); return true;
 	default: return false;
 	}
 }
 
 bool launch_stage_generic(const double* cur, double* nxt, const Geo& g, int s,
                           const AxisTable* tabs, const uint8_t* mat, hipStream_t st) {
-	switch (g.D) {
-	case 1: return launch_generic_d<1>(cur, nxt, g, s, tabs, mat, st);
-	case 2: return launch_generic_d<2>(cur, nxt, g, s, tabs, mat, st);
-	case 3: return launch_generic_d<3>(cur, nxt, g, s, tabs, mat, st);
+	// elastic contexts: M = pde_size(D); acoustic ones: M = D + 1 (in 1-D the two
+	// vectors have the same two components)
+	switch (g.D * 16 + g.M) {
+	case 1 * 16 + 2: return launch_generic_d<1, 2>(cur, nxt, g, s, tabs, mat, st);
+	case 2 * 16 + 5: return launch_generic_d<2, 5>(cur, nxt, g, s, tabs, mat, st);
+	case 3 * 16 + 9: return launch_generic_d<3, 9>(cur, nxt, g, s, tabs, mat, st);
+	case 2 * 16 + 3: return launch_generic_d<2, 3>(cur, nxt, g, s, tabs, mat, st);
+	case 3 * 16 + 4: return launch_generic_d<3, 4>(cur, nxt, g, s, tabs, mat, st);
 	default: return false;
 	}
 }

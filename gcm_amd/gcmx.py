@@ -28,6 +28,8 @@ PATH_AUTO, PATH_GENERIC, PATH_SPLIT, PATH_FUSED = 0, 1, 2, 3
 PATH_NAMES = {0: "auto", 1: "generic", 2: "split", 3: "fused"}
 SCHED_AUTO, SCHED_SINGLE, SCHED_XSLAB, SCHED_BFIRST = 0, 1, 2, 3
 FP_FMA, FP_EXACT = 0, 1
+MODEL_ELASTIC, MODEL_ACOUSTIC = 0, 1
+MODEL_NAMES = {MODEL_ELASTIC: "elastic", MODEL_ACOUSTIC: "acoustic"}
 UNIQUE_ID_BYTES = 128
 MAX_BORDER_Q = 16
 QUANTITY_CODES = {"Vx": 2, "Vy": 3, "Vz": 4, "Sxx": 5, "Sxy": 6, "Sxz": 7, "Syy": 8, "Syz": 9,
@@ -35,8 +37,8 @@ QUANTITY_CODES = {"Vx": 2, "Vy": 3, "Vz": 4, "Sxx": 5, "Sxy": 6, "Sxz": 7, "Syy"
 
 # Exported symbols, in header order (checked by tests/test_abi.py).
 SYMBOLS = [
-    "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_status_string",
-    "gcmx_create", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
+    "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_model_pde_size", "gcmx_status_string",
+    "gcmx_create", "gcmx_create_model", "gcmx_get_model", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
     "gcmx_upload", "gcmx_download", "gcmx_fill_random", "gcmx_stage", "gcmx_step",
     "gcmx_set_kernel_path", "gcmx_set_step_schedule", "gcmx_set_fp_mode", "gcmx_get_fp_mode", "gcmx_effective_path", "gcmx_last_step_path",
     "gcmx_border_fill",
@@ -111,6 +113,12 @@ def lib() -> ctypes.CDLL:
     L.gcmx_status_string.restype = ctypes.c_char_p
     L.gcmx_create.argtypes = [ctypes.POINTER(GridDesc), ctypes.c_int, ctypes.POINTER(vp)]
     L.gcmx_create.restype = st
+    L.gcmx_model_pde_size.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.gcmx_model_pde_size.restype = ctypes.c_int
+    L.gcmx_create_model.argtypes = [ctypes.POINTER(GridDesc), ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    L.gcmx_create_model.restype = st
+    L.gcmx_get_model.argtypes = [vp]
+    L.gcmx_get_model.restype = ctypes.c_int
     L.gcmx_destroy.argtypes = [vp]
     L.gcmx_destroy.restype = None
     L.gcmx_set_materials.argtypes = [vp, ctypes.c_int, dp, dp, dp]
@@ -209,19 +217,34 @@ def _ip(seq) -> ctypes.Array:
     return (ctypes.c_int * max(1, len(seq)))(*seq)
 
 
-def pde_size(dim: int) -> int:
+def pde_size(dim: int, model="elastic") -> int:
+    """Components of the PDE vector: elastic D + D(D+1)/2, acoustic D + 1
+    (velocity, then pressure at index D)."""
+    if _model_code(model) == MODEL_ACOUSTIC:
+        return dim + 1
     return dim + dim * (dim + 1) // 2
 
 
+def _model_code(model) -> int:
+    if model in MODEL_NAMES:
+        return int(model)
+    for code, name in MODEL_NAMES.items():
+        if model == name:
+            return code
+    raise ValueError(f"unknown model {model!r}: 'elastic' or 'acoustic'")
+
+
 class Context:
-    """One body (or one X-slab of a body) resident on one GPU."""
+    """One body (or one X-slab of a body) resident on one GPU.  `model`:
+    "elastic" (default) or "acoustic" (M = dim + 1 components: Vx.., pressure)."""
 
     def __init__(self, dim: int, border_size: int, sizes: Sequence[int],
                  start: Optional[Sequence[int]] = None, h: Optional[Sequence[float]] = None,
-                 device: int = 0):
+                 device: int = 0, model="elastic"):
         start = list(start) if start is not None else [0] * dim
         h = list(h) if h is not None else [1.0] * dim
-        self.dim, self.bs, self.M = dim, border_size, pde_size(dim)
+        self._model = _model_code(model)
+        self.dim, self.bs, self.M = dim, border_size, pde_size(dim, self._model)
         self.sizes = list(sizes)[:dim]
         self.start = start[:dim]
         self.h = h[:dim]
@@ -229,7 +252,10 @@ class Context:
                      (ctypes.c_int * 3)(*(self.start + [0] * (3 - dim))),
                      (ctypes.c_double * 3)(*(list(self.h) + [0.0] * (3 - dim))))
         self._ptr = ctypes.c_void_p()
-        _check(lib().gcmx_create(ctypes.byref(d), device, ctypes.byref(self._ptr)))
+        if self._model == MODEL_ELASTIC:
+            _check(lib().gcmx_create(ctypes.byref(d), device, ctypes.byref(self._ptr)))
+        else:
+            _check(lib().gcmx_create_model(ctypes.byref(d), self._model, device, ctypes.byref(self._ptr)))
         self.shape_all = tuple(s + 2 * border_size for s in self.sizes)
         self.n_all = int(np.prod(self.shape_all))
 
@@ -256,6 +282,11 @@ class Context:
     @property
     def ptr(self):
         return self._ptr
+
+    @property
+    def model(self) -> str:
+        """gcmx_get_model: "elastic" or "acoustic"."""
+        return MODEL_NAMES[lib().gcmx_get_model(self._ptr)]
 
     # -- set-up -----------------------------------------------------------
     def set_materials(self, U: np.ndarray, U1: np.ndarray, L: np.ndarray):
@@ -321,7 +352,7 @@ class Context:
         _check(lib().gcmx_set_fp_mode(self._ptr, mode))
 
     def matrix_structure(self) -> int:
-        """gcmx_matrix_structure: 0 general, 1 isotropic, 2 unrotated orthotropic."""
+        """gcmx_matrix_structure: 0 general, 1 isotropic, 2 unrotated orthotropic, 3 acoustic."""
         return int(lib().gcmx_matrix_structure(self._ptr))
 
     @property

@@ -25,6 +25,8 @@ def lib() -> ctypes.CDLL:
         L.gcm_host_orthotropic_from_isotropic.argtypes = [ctypes.c_double, ctypes.c_double,
                                                           ctypes.c_double, dp]
         L.gcm_host_orthotropic_from_isotropic.restype = None
+        L.gcm_host_acoustic_matrices.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_double, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -49,6 +51,17 @@ def orthotropic_elastic_matrices(rho: float, c):
     dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
     if lib().gcm_host_orthotropic_elastic_matrices(rho, dp(c), dp(U), dp(U1), dp(L)) != 0:
         raise ValueError("bad orthotropic material (needs rho > 0 and positive diagonal constants)")
+    return U, U1, L
+
+
+def acoustic_matrices(D: int, rho: float, lam: float, mu: float = 0.0):
+    """AcousticModel<D>::constructGcmMatrices (identity basis; mu is unused):
+    U, U1 [D,M,M], L [D,M] with M = D + 1 (velocity, then pressure)."""
+    M = D + 1
+    U = np.zeros((D, M, M)); U1 = np.zeros((D, M, M)); L = np.zeros((D, M))
+    dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    if lib().gcm_host_acoustic_matrices(D, rho, lam, mu, dp(U), dp(U1), dp(L)) != 0:
+        raise ValueError("bad acoustic material (needs rho > 0, lambda > 0)")
     return U, U1, L
 
 

@@ -120,6 +120,28 @@ struct PyEngine {
 		else c = as<3>().getMesh(id)->ctx();
 		return gcmx_matrix_structure(c);
 	}
+	gcmx_ctx* ctxOf(size_t id) {
+		if (D == 1) return as<1>().getMesh(id)->ctx();
+		if (D == 2) return as<2>().getMesh(id)->ctx();
+		return as<3>().getMesh(id)->ctx();
+	}
+	/// Per-kernel timing of the body's context on or off (gcmx_profile_enable).
+	void profile(size_t id, bool on) { gcmxCheck(gcmx_profile_enable(ctxOf(id), on ? 1 : 0), "gcmx_profile_enable"); }
+	/// The kernel instances the body's profiled launches ran (gcmx_profile_kernel), in bucket order.
+	std::vector<std::string> profileKernels(size_t id) {
+		gcmx_ctx* c = ctxOf(id);
+		std::vector<std::string> out;
+		const int n = gcmx_profile_read(c, -1, nullptr, nullptr, nullptr, nullptr);
+		for (int i = 0; i < n; i++) {
+			const char* name = nullptr;
+			double ms = 0, bytes = 0;
+			long long launches = 0;
+			gcmx_profile_read(c, i, &name, &ms, &launches, &bytes);
+			const char* k = gcmx_profile_kernel(c, i);
+			if (launches > 0 && k && *k) out.push_back(k);
+		}
+		return out;
+	}
 	real maximalEigenvalue(size_t id) {
 		if (D == 1) return as<1>().getMesh(id)->getMaximalEigenvalue();
 		if (D == 2) return as<2>().getMesh(id)->getMaximalEigenvalue();
@@ -136,14 +158,14 @@ py::dict hostState(const Task& task, size_t id) {
 	for (int i = 0; i < D; i++) shape.push_back(grid.sizes[i] + 2 * grid.borderSize);
 	py::array_t<uint8_t> ids(shape);
 	std::copy(st.matId.begin(), st.matId.end(), ids.mutable_data());
-	shape.push_back(pdeSize(D));
+	shape.push_back(st.M);
 	py::array_t<real> pde(shape);
 	std::copy(st.pde.begin(), st.pde.end(), pde.mutable_data());
 	py::dict d;
 	d["pde"] = pde;
 	d["mat_ids"] = ids;
 	d["maximal_eigenvalue"] = st.maximalEigenvalue;
-	d["n_conditions"] = st.matrices.size();
+	d["n_conditions"] = st.numberOfConditions();
 	return d;
 }
 
@@ -162,7 +184,7 @@ void writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::
 	makeParentDirectories(fileName);
 	cubic::writeVtkSnapshot<D>(fileName, grid.sizes, grid.start, grid.h, grid.borderSize,
 	                           layer.data(), st.matId.data(), st.materialNumber,
-	                           task.vtkSnapshotter.quantitiesToSnap);
+	                           task.vtkSnapshotter.quantitiesToSnap, st.model);
 }
 
 /// One body of the GPU-free simplex set-up (simplex::buildHostPlans) as numpy arrays.
@@ -293,15 +315,19 @@ PYBIND11_MODULE(_gcm_host, m) {
 	    .def_property("h", [](Task& t) { return t.cubicGrid.h; },
 	                  [](Task& t, std::vector<real> h) { t.cubicGrid.h = h; })
 	    .def("add_body",
-	         [](Task& t, size_t id, std::vector<int> sizes, std::vector<int> start) {
+	         [](Task& t, size_t id, std::vector<int> sizes, std::vector<int> start, const std::string& model) {
+		         if (model != "elastic" && model != "acoustic") throw Exception("unknown model " + model);
 		         t.bodies[id] = Task::Body();
+		         t.bodies[id].modelId = model == "acoustic" ? Models::T::ACOUSTIC : Models::T::ELASTIC;
 		         t.cubicGrid.cubics[id] = {sizes, start};
 		         // a body added after an orthotropic material that covers it is of that kind
 		         const auto& mc = t.materialConditions;
 		         if (mc.type == Task::MaterialCondition::Type::BY_AREAS ? mc.byAreas.defaultOrthotropic != nullptr
 		                                                                  : mc.byBodies.bodyOrthotropicMap.count(id) > 0)
 			         t.bodies[id].materialId = Materials::T::ORTHOTROPIC;
-	         })
+	         },
+	         py::arg("id"), py::arg("sizes"), py::arg("start"), py::arg("model") = "elastic",
+	         "Task::Body + its cube; model: \"elastic\" or \"acoustic\" (Task::Body::modelId)")
 	    .def("set_default_material",
 	         [](Task& t, real rho, real lam, real mu, real tau0, int number) {
 		         t.materialConditions.type = Task::MaterialCondition::Type::BY_AREAS;
@@ -472,6 +498,31 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         },
 	         py::arg("type"), py::arg("pair") = py::none(),
 	         "Task::contactCondition: the default, or the condition of one pair of bodies");
+
+	m.def(
+	    "acoustic_matrices",
+	    [](int D, real rho, real lambda, real mu) {
+		    auto run = [&](auto tag) {
+			    constexpr int DD = decltype(tag)::value;
+			    constexpr ssize_t M = DD + 1;
+			    AcousticMatrices<DD> am;
+			    AcousticModel<DD>::constructGcmMatrices(am, IsotropicMaterial(rho, lambda, mu));
+			    py::array_t<real> U({(ssize_t)DD, M, M}), U1({(ssize_t)DD, M, M}), A({(ssize_t)DD, M, M}), L({(ssize_t)DD, M});
+			    for (int s = 0; s < DD; s++) {
+				    std::copy(am.m[s].U.begin(), am.m[s].U.end(), U.mutable_data() + s * M * M);
+				    std::copy(am.m[s].U1.begin(), am.m[s].U1.end(), U1.mutable_data() + s * M * M);
+				    std::copy(am.m[s].A.begin(), am.m[s].A.end(), A.mutable_data() + s * M * M);
+				    std::copy(am.m[s].L.begin(), am.m[s].L.end(), L.mutable_data() + s * M);
+			    }
+			    return py::make_tuple(U, U1, L, A);
+		    };
+		    if (D == 1) return run(std::integral_constant<int, 1>());
+		    if (D == 2) return run(std::integral_constant<int, 2>());
+		    if (D == 3) return run(std::integral_constant<int, 3>());
+		    throw Exception("dimensionality must be 1, 2 or 3");
+	    },
+	    "AcousticModel<D>::constructGcmMatrices, identity basis: (U, U1 [D, M, M], L [D, M], A [D, M, M]), M = D + 1",
+	    py::arg("dim"), py::arg("rho"), py::arg("lam"), py::arg("mu") = 0.0);
 
 	m.def(
 	    "host_state",
@@ -663,8 +714,12 @@ PYBIND11_MODULE(_gcm_host, m) {
 	    .def("path", &PyEngine::path)
 	    .def("last_path", &PyEngine::lastPath)
 	    .def("ode_fused", &PyEngine::odeFused)
-	    .def("matrix_structure", &PyEngine::matrixStructure, "0 general, 1 isotropic, 2 orthotropic")
+	    .def("matrix_structure", &PyEngine::matrixStructure, "0 general, 1 isotropic, 2 orthotropic, 3 acoustic")
 	    .def("sync", &PyEngine::sync, py::arg("body") = 0)
+	    .def("profile", &PyEngine::profile, py::arg("body") = 0, py::arg("enable") = true,
+	         "per-kernel timing of the body's context (gcmx_profile_enable)")
+	    .def("profile_kernels", &PyEngine::profileKernels, py::arg("body") = 0,
+	         "kernel instances the body's profiled launches ran (gcmx_profile_kernel)")
 	    .def("maximal_eigenvalue", &PyEngine::maximalEigenvalue)
 	    .def_property_readonly("steps", [](PyEngine& p) { return p.e->stepsDone(); })
 	    .def_property_readonly("required_time", [](PyEngine& p) { return p.e->getRequiredTime(); })

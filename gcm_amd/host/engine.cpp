@@ -123,9 +123,11 @@ static void forEachInner(const std::array<int, D>& sizes, F f, int axis = -1, in
 // -------------------------------------------------------------------- HipMesh --
 
 template <int D>
-HipMesh<D>::HipMesh(const Task&, size_t id_, const typename CubicGrid<D>::ConstructionPack& cp,
+HipMesh<D>::HipMesh(const Task& task, size_t id_, const typename CubicGrid<D>::ConstructionPack& cp,
                     int device_)
     : AbstractMesh<D>(id_, cp), device(device_) {
+	const auto tb = task.bodies.find(id_);
+	if (tb != task.bodies.end()) model_ = tb->second.modelId;
 	gcmx_grid_desc desc{};
 	desc.dim = D;
 	desc.border_size = cp.borderSize;
@@ -134,7 +136,8 @@ HipMesh<D>::HipMesh(const Task&, size_t id_, const typename CubicGrid<D>::Constr
 		desc.start[i] = i < D ? cp.start[i] : 0;
 		desc.h[i] = i < D ? cp.h[i] : 0;
 	}
-	gcmxCheck(gcmx_create(&desc, device, &ctx_), "gcmx_create");
+	gcmxCheck(gcmx_create_model(&desc, model_ == Models::T::ACOUSTIC ? GCMX_MODEL_ACOUSTIC : GCMX_MODEL_ELASTIC,
+	                            device, &ctx_), "gcmx_create_model");
 }
 
 template <int D>
@@ -276,8 +279,14 @@ typename CubicGrid<D>::ConstructionPack constructionPack(const Task& task, size_
 // the data would be stored, without touching a GPU.
 template <int D>
 HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
-	constexpr int M = pdeSize(D);
+	constexpr int MX = pdeSize(D);  // the elastic vector; the acoustic one (D + 1) is no longer
 	HostState<D> st;
+	const auto body = task.bodies.find(grid.id);
+	const Models::T model = body != task.bodies.end() ? body->second.modelId : Models::T::ELASTIC;
+	const bool acoustic = model == Models::T::ACOUSTIC;
+	const int M = pdeSizeOf(model, D);
+	st.model = model;
+	st.M = M;
 	const long long nAll = grid.sizeOfAllNodes();
 	st.pde.assign((size_t)nAll * M, 0.0);
 	st.matId.assign((size_t)nAll, 0);
@@ -296,7 +305,6 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 	};
 	std::vector<Cond> conds;
 	const auto& mc = task.materialConditions;
-	const auto body = task.bodies.find(grid.id);
 	const Materials::T kind = body != task.bodies.end() ? body->second.materialId : Materials::T::ISOTROPIC;
 	if (mc.type == MC::Type::BY_AREAS) {
 		conds.push_back({std::make_shared<InfiniteArea>(), mc.byAreas.defaultMaterial, mc.byAreas.defaultOrthotropic});
@@ -311,10 +319,18 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 		                 o != mc.byBodies.bodyOrthotropicMap.end() ? o->second : nullptr});
 	}
 	if (conds.size() > 255) throw Exception("at most 255 material conditions per body");
-	matrices.assign(conds.size(), GcmMatrices<D>());
+	if (acoustic && kind != Materials::T::ISOTROPIC) throw Exception("acoustic bodies take isotropic materials only");
+	if (acoustic) st.acousticMatrices.assign(conds.size(), AcousticMatrices<D>());
+	else matrices.assign(conds.size(), GcmMatrices<D>());
 	st.tau0.assign(conds.size(), 0);
 	for (size_t c = 0; c < conds.size(); c++) {
-		if (kind == Materials::T::ORTHOTROPIC) {
+		if (acoustic) {  // ISOTROPIC x ACOUSTIC: rho and lambda only, mu may be 0
+			if (conds[c].ortho) throw Exception("orthotropic material in an ACOUSTIC body");
+			if (!conds[c].iso) throw Exception("material condition without a material");
+			AcousticModel<D>::constructGcmMatrices(st.acousticMatrices[c], *conds[c].iso);
+			st.tau0[c] = conds[c].iso->tau0;
+			st.materialNumber.push_back(conds[c].iso->materialNumber);
+		} else if (kind == Materials::T::ORTHOTROPIC) {
 			const MC::Orthotropic m = MC::orthotropicOf(conds[c].iso, conds[c].ortho);
 			if (!m) throw Exception("material condition without a material");
 			ElasticModel<D>::constructGcmMatrices(matrices[c], *m);
@@ -336,23 +352,28 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 	st.maximalEigenvalue = 0;
 	for (const auto& m : matrices)
 		st.maximalEigenvalue = std::fmax(st.maximalEigenvalue, m.getMaximalEigenvalue());
+	for (const auto& m : st.acousticMatrices)
+		st.maximalEigenvalue = std::fmax(st.maximalEigenvalue, m.getMaximalEigenvalue());
 
 	// ---- InitialCondition::apply (util/task/InitialCondition.hpp:23-88)
-	std::vector<std::pair<std::shared_ptr<Area>, std::array<real, M>>> ics;
+	std::vector<std::pair<std::shared_ptr<Area>, std::array<real, MX>>> ics;  // the first M entries
 	for (const auto& v : task.initialCondition.vectors) {
 		if ((int)v.list.size() != M) throw Exception("initial vector has the wrong size");
-		std::array<real, M> a{};
+		std::array<real, MX> a{};
 		std::copy(v.list.begin(), v.list.end(), a.begin());
 		ics.push_back({v.area, a});
 	}
 	{
-		const GcmMatrices<D>& front = matrices.front();  // mcConditions.front().material
+		// mcConditions.front().material; an S wave or a stress quantity on an acoustic
+		// body throws, as the reference's map lookups would (Model.cpp:55-60)
 		for (const auto& w : task.initialCondition.waves) {
 			if (!(w.direction >= 0 && w.direction < D)) throw Exception("wave direction out of range");
-			const int col = waveColumn(D, w.waveType, kind);
-			std::array<real, M> tmp{};
-			for (int r = 0; r < M; r++) tmp[r] = front.m[w.direction].U1[r * M + col];
-			const real current = getQuantity(D, w.quantity, tmp.data());
+			const int col = acoustic ? acousticWaveColumn(w.waveType) : waveColumn(D, w.waveType, kind);
+			std::array<real, MX> tmp{};
+			for (int r = 0; r < M; r++)
+				tmp[r] = acoustic ? st.acousticMatrices.front().m[w.direction].U1[r * M + col]
+				                  : matrices.front().m[w.direction].U1[r * M + col];
+			const real current = getQuantityOf(model, D, w.quantity, tmp.data());
 			if (current == 0) throw Exception("wave calibration quantity is zero");
 			const real f = w.quantityValue / current;
 			for (int r = 0; r < M; r++) tmp[r] *= f;
@@ -360,8 +381,9 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 		}
 	}
 	for (const auto& q : task.initialCondition.quantities) {
-		std::array<real, M> tmp{};
-		setQuantity(D, q.physicalQuantity, q.value, tmp.data());
+		std::array<real, MX> tmp{};
+		if (acoustic) setAcousticQuantity(D, q.physicalQuantity, q.value, tmp.data());
+		else setQuantity(D, q.physicalQuantity, q.value, tmp.data());
 		ics.push_back({q.area, tmp});
 	}
 	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
@@ -380,26 +402,37 @@ void HipMesh<D>::setUpPde(const Task& task) {
 	if (pdeIsSetUp) throw Exception("setUpPde called twice");
 	pdeIsSetUp = true;
 	HostState<D> st = buildHostState<D>(task, *this);
+	if (st.model != model_) throw Exception("the body's model changed after its mesh was created");
 	matrices = st.matrices;
+	acousticMatrices = st.acousticMatrices;
 	maximalEigenvalue = st.maximalEigenvalue;
 	auto& matId = st.matId;
 	materialNumbers_ = st.materialNumber;
-	if (matrices.size() > 1) matIdAll_ = matId;  // before the device remap below
+	const size_t nCond = st.numberOfConditions();
+	const int M = st.M;  // the model's components per node
+	if (nCond > 1) matIdAll_ = matId;  // before the device remap below
 
 	// ---- device tables: only the materials the nodes actually use
-	std::vector<int> used(matrices.size(), 0);
+	std::vector<int> used(nCond, 0);
 	forEachInner<D>(this->sizes, [&](const IntD& it) { used[matId[(size_t)this->getIndex(it)]] = 1; });
-	std::vector<int> remap(matrices.size(), -1);
+	std::vector<int> remap(nCond, -1);
 	int nUsed = 0;
-	for (size_t c = 0; c < matrices.size(); c++)
+	for (size_t c = 0; c < nCond; c++)
 		if (used[c]) remap[c] = nUsed++;
 	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
 	deviceTau0_.assign(nUsed, 0);
-	for (size_t c = 0; c < matrices.size(); c++) {
+	for (size_t c = 0; c < nCond; c++) {
 		if (remap[c] < 0) continue;
 		deviceTau0_[remap[c]] = st.tau0[c];
 		for (int s = 0; s < D; s++) {
 			const size_t o = ((size_t)remap[c] * D + s);
+			if (model_ == Models::T::ACOUSTIC) {
+				const auto& m = acousticMatrices[c].m[s];
+				std::copy(m.U.begin(), m.U.end(), U.begin() + o * M * M);
+				std::copy(m.U1.begin(), m.U1.end(), U1.begin() + o * M * M);
+				std::copy(m.L.begin(), m.L.end(), L.begin() + o * M);
+				continue;
+			}
 			std::copy(matrices[c].m[s].U.begin(), matrices[c].m[s].U.end(), U.begin() + o * M * M);
 			std::copy(matrices[c].m[s].U1.begin(), matrices[c].m[s].U1.end(), U1.begin() + o * M * M);
 			std::copy(matrices[c].m[s].L.begin(), matrices[c].m[s].L.end(), L.begin() + o * M);
@@ -415,6 +448,7 @@ void HipMesh<D>::setUpPde(const Task& task) {
 
 template <int D>
 std::vector<real> HipMesh<D>::pdeAll() const {
+	const int M = pdeM();
 	std::vector<real> out((size_t)this->sizeOfAllNodes() * M);
 	if (stack_) {  // this member's part of the stack (its ghost layers at a contact:
 		           // the neighbour's inner layers, as the contact copy leaves them)
@@ -435,9 +469,10 @@ std::vector<real> HipMesh<D>::pdeAll() const {
 template <int D>
 std::array<real, HipMesh<D>::M> HipMesh<D>::pde(const IntD& it) const {
 	const std::vector<real> all = pdeAll();
-	std::array<real, M> v;
+	std::array<real, M> v{};
 	const size_t i = (size_t)this->getIndex(it);
-	for (int c = 0; c < M; c++) v[c] = all[i * M + c];
+	const int m = pdeM();
+	for (int c = 0; c < m; c++) v[c] = all[i * m + c];
 	return v;
 }
 
@@ -481,7 +516,7 @@ HipBorderConditions<D>::HipBorderConditions(const Task& task, const HipMesh<D>& 
 			c.direction = bc.direction;
 			if (!(bc.direction >= 0 && bc.direction < D)) throw Exception("border direction out of range");
 			for (const auto& q : bc.values) {
-				if (!hasQuantity(D, q.first)) throw Exception("border quantity not in the PDE vector");
+				if (!hasQuantityOf(mesh.model(), D, q.first)) throw Exception("border quantity not in the PDE vector");
 				c.values.push_back({q.first, q.second});  // std::map order == reference order
 			}
 			if (c.values.size() > GCMX_MAX_BORDER_Q) throw Exception("too many border quantities");
@@ -666,8 +701,22 @@ void Engine<D>::createGridsAndContacts(const Task& task) {
 	if (task.bodies.empty()) throw Exception("the task has no bodies");
 	if (task.bodies.size() != task.cubicGrid.cubics.size())
 		throw Exception("every body needs a cube");
+	// The three products of Engine<D>::createAbstractFactory (Engine.cpp:155-189):
+	// ISOTROPIC x ELASTIC, ORTHOTROPIC x ELASTIC, ISOTROPIC x ACOUSTIC.  An
+	// acoustic body stands alone (contacts and stacks are elastic-only here) and
+	// has no ODE (AcousticModel::OdeVariables is void).
+	size_t nAcoustic = 0;
+	for (const auto& tb : task.bodies) nAcoustic += tb.second.modelId == Models::T::ACOUSTIC;
+	if (nAcoustic > 0 && nAcoustic < task.bodies.size()) throw Exception("a task must not mix acoustic and elastic bodies");
+	if (nAcoustic > 1) throw Exception("at most one acoustic body (contacts between acoustic bodies are not implemented)");
 	for (const auto& tb : task.bodies) {
-		if (tb.second.modelId != Models::T::ELASTIC) throw Exception("only elastic bodies are on this path");
+		if (tb.second.modelId != Models::T::ELASTIC && tb.second.modelId != Models::T::ACOUSTIC)
+			throw Exception("unknown model");
+		if (tb.second.modelId == Models::T::ACOUSTIC) {
+			if (tb.second.materialId != Materials::T::ISOTROPIC)
+				throw Exception("ORTHOTROPIC x ACOUSTIC is not a product of the cubic engine");
+			if (!tb.second.odes.empty()) throw Exception("the acoustic model has no ODE");
+		}
 		if (tb.second.materialId == Materials::T::ORTHOTROPIC && D != 3)
 			throw Exception("orthotropic media are implemented in 3-D only");
 		Body body;
@@ -925,7 +974,7 @@ void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) 
 	writeVtkSnapshot<D>(makeFileNameForSnapshot(std::to_string(mesh->id), step, "vts", "vtk"),
 	                    mesh->sizes, mesh->start, mesh->h, mesh->borderSize, pde.data(),
 	                    ids.empty() ? nullptr : ids.data(), mesh->materialNumbers(),
-	                    quantitiesToSnap);
+	                    quantitiesToSnap, mesh->model());
 }
 
 template <int D>
@@ -942,7 +991,7 @@ template <int D>
 void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) {
 	const HipMesh<D>* mesh = dynamic_cast<const HipMesh<D>*>(mesh_);
 	if (!mesh) throw Exception("SliceSnapshotter: not a cubic mesh");
-	constexpr int M = pdeSize(D);
+	const int M = mesh->pdeM();
 	const int direction = D - 1;
 	const std::vector<real> pde = mesh->pdeAll();
 	auto at = [&](const std::array<int, D>& it) { return &pde[(size_t)mesh->getIndex(it) * M]; };
@@ -963,7 +1012,7 @@ void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step
 	forEachInner<D>(mesh->sizes, [&](const std::array<int, D>& j) {
 		if (j[direction] != mesh->sizes[direction] - 1) return;
 		if (detectionArea->contains(mesh->coords(j)))
-			valuesInArea.push_back(getQuantity(D, quantityToWrite, at(j)));
+			valuesInArea.push_back(getQuantityOf(mesh->model(), D, quantityToWrite, at(j)));
 	});
 	if (valuesInArea.empty()) throw Exception("SliceSnapshotter: no node in the detection area");
 	real sum = 0;

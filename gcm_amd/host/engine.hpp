@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/gcmx.h"
+#include "acoustic_model.hpp"
 #include "snapshot.hpp"
 #include "task.hpp"
 
@@ -127,6 +128,12 @@ struct HostState {
 	std::vector<real> pde;
 	std::vector<uint8_t> matId;
 	std::vector<GcmMatrices<D>> matrices;
+	/// An ACOUSTIC body (Task::Body::modelId): M = D + 1 components per node
+	/// (velocity, then pressure) and AcousticModel matrices; `matrices` stays empty.
+	Models::T model = Models::T::ELASTIC;
+	int M = pdeSize(D);
+	std::vector<AcousticMatrices<D>> acousticMatrices;
+	size_t numberOfConditions() const { return model == Models::T::ACOUSTIC ? acousticMatrices.size() : matrices.size(); }
 	std::vector<real> tau0;  // tau0 of the material (either kind) per material condition
 	std::vector<int> materialNumber;  // its materialNumber per condition
 	real maximalEigenvalue = 0;
@@ -144,8 +151,11 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid);
 template <int D>
 class HipMesh : public AbstractMesh<D> {
 public:
-	static constexpr int M = pdeSize(D);
+	static constexpr int M = pdeSize(D);  ///< of an elastic body; an acoustic one holds pdeM() <= M
 	typedef typename CubicGrid<D>::IntD IntD;
+	/// The body's model (Task::Body::modelId) and the components per node it holds.
+	Models::T model() const { return model_; }
+	int pdeM() const { return pdeSizeOf(model_, D); }
 	HipMesh(const Task& task, size_t id, const typename CubicGrid<D>::ConstructionPack& cp,
 	        int device);
 	~HipMesh() override;
@@ -158,9 +168,10 @@ public:
 	gcmx_ctx* ctx() const { return ctx_; }
 	/// Current layer in the reference AoS all-nodes order (downloads).
 	std::vector<real> pdeAll() const;
-	/// One node's PDE vector (downloads the layer; for tests and snapshots).
+	/// One node's PDE vector (downloads the layer; for tests and snapshots); an
+	/// acoustic body fills the first pdeM() entries.
 	std::array<real, M> pde(const IntD& it) const;
-	int numberOfMaterials() const { return (int)matrices.size(); }
+	int numberOfMaterials() const { return (int)(model_ == Models::T::ACOUSTIC ? acousticMatrices.size() : matrices.size()); }
 	/// tau0 of the materials in the device table order (gcmx_set_materials).
 	const std::vector<real>& deviceTau0() const { return deviceTau0_; }
 	/// Material-condition index per node (all-nodes order) and the conditions'
@@ -194,6 +205,8 @@ private:
 	int device;
 	real maximalEigenvalue = 0;
 	std::vector<GcmMatrices<D>> matrices;  // one per material condition
+	Models::T model_ = Models::T::ELASTIC;
+	std::vector<AcousticMatrices<D>> acousticMatrices;  // the same for an acoustic body
 	std::vector<real> deviceTau0_;
 	std::vector<uint8_t> matIdAll_;
 	std::vector<int> materialNumbers_;
@@ -345,7 +358,9 @@ public:
 };
 
 /// AbstractFactory<ElasticModel<D>, CubicGrid<D>, IsotropicMaterial, HipMesh>; a body whose
-/// Task::Body::materialId is ORTHOTROPIC is built with OrthotropicMaterial (buildHostState)
+/// Task::Body::materialId is ORTHOTROPIC is built with OrthotropicMaterial, one whose
+/// modelId is ACOUSTIC with AcousticModel<D> (buildHostState): the three products of
+/// Engine<D>::createAbstractFactory (engine/cubic/Engine.cpp:155-189)
 template <int D>
 class HipFactory : public AbstractFactoryBase<D> {
 public:

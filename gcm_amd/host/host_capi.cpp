@@ -1,4 +1,5 @@
 // host_capi.cpp -- C entry points of the host mirror used by the Python side.
+#include "acoustic_model.hpp"
 #include "elastic_model.hpp"
 
 extern "C" {
@@ -48,6 +49,35 @@ int gcm_host_orthotropic_elastic_matrices(double rho, const double* c, double* U
 			for (int k = 0; k < 9; k++) L[s * 9 + k] = m.m[s].L[k];
 		}
 		return 0;
+	} catch (...) {
+		return -1;
+	}
+}
+
+/// AcousticModel<D>::constructGcmMatrices for an isotropic material (mu unused),
+/// identity basis: U, U1 [D][M*M] row-major, L [D][M], M = D + 1.  Returns 0 or
+/// -1 (bad input).
+int gcm_host_acoustic_matrices(int D, double rho, double lambda, double mu, double* U, double* U1, double* L) {
+	try {
+		auto run = [&](auto tag) {
+			constexpr int DD = decltype(tag)::value;
+			constexpr int M = gcm::acousticPdeSize(DD);
+			gcm::AcousticMatrices<DD> m;
+			gcm::AcousticModel<DD>::constructGcmMatrices(m, gcm::IsotropicMaterial(rho, lambda, mu));
+			for (int s = 0; s < DD; s++) {
+				for (int i = 0; i < M * M; i++) {
+					U[s * M * M + i] = m.m[s].U[i];
+					U1[s * M * M + i] = m.m[s].U1[i];
+				}
+				for (int k = 0; k < M; k++) L[s * M + k] = m.m[s].L[k];
+			}
+		};
+		switch (D) {
+		case 1: run(std::integral_constant<int, 1>()); return 0;
+		case 2: run(std::integral_constant<int, 2>()); return 0;
+		case 3: run(std::integral_constant<int, 3>()); return 0;
+		default: return -1;
+		}
 	} catch (...) {
 		return -1;
 	}

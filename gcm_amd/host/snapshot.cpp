@@ -1,6 +1,8 @@
 // snapshot.cpp -- file writers of the snapshotters (see snapshot.hpp).
 #include "snapshot.hpp"
 
+#include "acoustic_model.hpp"
+
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -208,8 +210,8 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
                       const std::array<int, D>& start, const std::array<real, D>& h,
                       int borderSize, const real* pdeAll, const uint8_t* matIdAll,
                       const std::vector<int>& materialNumbers,
-                      const std::vector<PhysicalQuantities::T>& quantities) {
-	constexpr int M = pdeSize(D);
+                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model) {
+	const int M = pdeSizeOf(model, D);
 	int dims[3] = {1, 1, 1};
 	for (int i = 0; i < D; i++) dims[i] = sizes[i];
 	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
@@ -223,7 +225,7 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 	VtsArray vel{"Velocity", 3, std::vector<float>(3 * n)};
 	std::vector<VtsArray> qs;
 	for (auto q : quantities) {
-		if (!hasQuantity(D, q)) throw Exception("quantity to snap is not in this PDE vector");
+		if (!hasQuantityOf(model, D, q)) throw Exception("quantity to snap is not in this PDE vector");
 		qs.push_back(VtsArray{quantityName(q), 1, std::vector<float>(n)});
 	}
 	VtsArray mat{"material_index", 1, std::vector<float>(n)};
@@ -242,7 +244,7 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 					vel.values[3 * p + i] = i < D ? (float)v[i] : 0.0f;  // getVelocity, padded
 				}
 				for (size_t k = 0; k < qs.size(); k++)
-					qs[k].values[p] = (float)getQuantity(D, quantities[k], v);
+					qs[k].values[p] = (float)getQuantityOf(model, D, quantities[k], v);
 				const int m = matIdAll ? matIdAll[idx] : 0;
 				mat.values[p] = (float)materialNumbers.at((size_t)m);
 			}
@@ -256,15 +258,15 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 template void writeVtkSnapshot<1>(const std::string&, const std::array<int, 1>&,
                                   const std::array<int, 1>&, const std::array<real, 1>&, int,
                                   const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&);
+                                  const std::vector<PhysicalQuantities::T>&, Models::T);
 template void writeVtkSnapshot<2>(const std::string&, const std::array<int, 2>&,
                                   const std::array<int, 2>&, const std::array<real, 2>&, int,
                                   const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&);
+                                  const std::vector<PhysicalQuantities::T>&, Models::T);
 template void writeVtkSnapshot<3>(const std::string&, const std::array<int, 3>&,
                                   const std::array<int, 3>&, const std::array<real, 3>&, int,
                                   const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&);
+                                  const std::vector<PhysicalQuantities::T>&, Models::T);
 
 }  // namespace cubic
 }  // namespace gcm

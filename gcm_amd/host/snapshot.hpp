@@ -113,12 +113,15 @@ void writeVts(const std::string& fileName, const int dims[3], const std::vector<
 /// layer in the reference AoS all-nodes order: "Velocity" (3 components, zero
 /// padded), each quantity of `quantities` by its PhysicalQuantities::NAME, and
 /// "material_index" (IsotropicMaterial::materialNumber of the node).  GPU-free.
+/// `model`: what the layer's vectors hold -- ACOUSTIC: D + 1 components, the
+/// quantities of AcousticVariables (the velocity components and PRESSURE).
 template <int D>
 void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& sizes,
                       const std::array<int, D>& start, const std::array<real, D>& h,
                       int borderSize, const real* pdeAll, const uint8_t* matIdAll,
                       const std::vector<int>& materialNumbers,
-                      const std::vector<PhysicalQuantities::T>& quantities);
+                      const std::vector<PhysicalQuantities::T>& quantities,
+                      Models::T model = Models::T::ELASTIC);
 
 const char* quantityName(PhysicalQuantities::T q);
 

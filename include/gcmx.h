@@ -83,10 +83,23 @@ typedef enum gcmx_schedule {
 	                          the same stream; needs X >= 4*bs    */
 } gcmx_schedule;
 
+/* The wave model of a context (gcmx_create_model): what the PDE vector holds.
+ * ELASTIC: VelocitySigmaVariables<D>, Vx..V(D-1) then the stress components,
+ * M = D + D(D+1)/2.  ACOUSTIC: AcousticVariables<D>
+ * (rheology/variables/AcousticVariables.hpp), Vx..V(D-1) then the pressure at
+ * index D, M = D + 1. */
+typedef enum gcmx_model {
+	GCMX_MODEL_ELASTIC = 0,
+	GCMX_MODEL_ACOUSTIC = 1
+} gcmx_model;
+
 /* ---- library ------------------------------------------------------------ */
 int         gcmx_abi_version(void);
 const char* gcmx_last_error(void);
 int         gcmx_pde_size(int dim); /* VelocitySigmaVariables<D>: D + D(D+1)/2 */
+/* Components of a model's PDE vector (-1 for a bad model or dim): elastic as
+ * gcmx_pde_size, acoustic dim + 1. */
+int         gcmx_model_pde_size(gcmx_model model, int dim);
 const char* gcmx_status_string(gcmx_status s);
 
 /* ---- lifetime --------------------------------------------------------------
@@ -95,6 +108,25 @@ const char* gcmx_status_string(gcmx_status s);
  * and CubicGrid ctor assertions (grid/cubic/CubicGrid.hpp:184-199).
  * Allocates two zero-filled time layers on `device`. */
 gcmx_status gcmx_create(const gcmx_grid_desc* desc, int device, gcmx_ctx** out);
+/* The same for a given wave model; gcmx_create is gcmx_create_model(desc,
+ * GCMX_MODEL_ELASTIC, device, out).  An acoustic context (ISOTROPIC x ACOUSTIC of
+ * Engine<D>::createAbstractFactory, engine/cubic/Engine.cpp:155-189) holds
+ * M = dim + 1 components per node, Vx..V(dim-1) then the pressure at index dim:
+ * every array of this interface (gcmx_set_materials' [n_mat][dim][M][M] matrices,
+ * gcmx_upload / gcmx_download, gcmx_fill_random) takes that M.  On it
+ *  - border quantities (gcmx_border_fill, gcmx_border_apply, gcmx_step_faces,
+ *    gcmx_step_face_map) are Vx..Vz (2..4) and PRESSURE (12), which addresses
+ *    component dim directly (AcousticVariables::QUANTITIES); a stress code is
+ *    GCMX_ERR_INVALID_ARG.  The ghost rule is the elastic one: mirror, then
+ *    -inner + 2 f(t) on the named components;
+ *  - gcmx_ode_maxwell and gcmx_step_ode (AcousticModel::OdeVariables is void)
+ *    and gcmx_comm_init* (no X slabs yet) return GCMX_ERR_UNSUPPORTED;
+ *  - gcmx_set_fp_mode is accepted and changes nothing: the acoustic one-pass
+ *    step has one build, which keeps the reference's roundings. */
+gcmx_status gcmx_create_model(const gcmx_grid_desc* desc, gcmx_model model, int device, gcmx_ctx** out);
+/* The model a context was created with; a NULL context answers
+ * GCMX_MODEL_ELASTIC (the function has no error return). */
+gcmx_model  gcmx_get_model(const gcmx_ctx* ctx);
 void        gcmx_destroy(gcmx_ctx* ctx);
 
 /* ---- set-up ----------------------------------------------------------------
@@ -110,11 +142,17 @@ void        gcmx_destroy(gcmx_ctx* ctx);
  * L = (-, +), shear pairs first): one material without per-node ids, or, with
  * per-node ids, 1..32 materials every one of which has that structure (a set
  * mixing isotropic-pattern and orthotropic materials counts as general).  The
- * recognition is redone by gcmx_set_material_ids, so the call order is free. */
+ * recognition is redone by gcmx_set_material_ids, so the call order is free.
+ * On an acoustic context the AcousticModel matrices for the identity basis are
+ * recognised (AcousticModel.hpp:214-317: rows 0 / 1 of U read the axis velocity
+ * with 0.5 and the pressure with opposite coefficients, L = (+c, -c, 0..), each
+ * zero mode one entry of magnitude 1, either sign, on one tangential velocity):
+ * one material without per-node ids; per-node ids run the generic stages. */
 gcmx_status gcmx_set_materials(gcmx_ctx* ctx, int n_mat, const double* U,
                                const double* U1, const double* L);
 /* Structure recognised in the matrices of the last gcmx_set_materials:
- * 0 general, 1 isotropic, 2 unrotated orthotropic (0 before materials are set). */
+ * 0 general, 1 isotropic, 2 unrotated orthotropic, 3 acoustic (acoustic contexts
+ * only; 0 before materials are set). */
 int         gcmx_matrix_structure(gcmx_ctx* ctx);
 /* One byte per node of the all-nodes array (getIndex order); NULL means every
  * node uses material 0.  Ghost entries are ignored.  With per-node ids the 3-D
@@ -157,6 +195,13 @@ gcmx_status gcmx_stage(gcmx_ctx* ctx, int axis, double tau);
  * node's own tables under the same conditions when, for this tau, floor(q) = 0
  * for every material, and Z <= 512 (1024 at borderSize 1); any other tau or
  * size runs the generic per-stage kernel with identical results.
+ * Acoustic contexts (gcmx_matrix_structure 3), 3-D: the one-pass step
+ * k_step_acoustic (64 B per node-step) with one material, no per-node ids,
+ * borderSize <= 3, 2 * borderSize <= Z <= 1024, no ghost ever written and the
+ * path AUTO or FUSED, when for this tau each axis's two feet lie on the sides
+ * the kernel reads and q != 0 (any floor(q) < borderSize: Courant 1 puts the
+ * foot on a node); otherwise, in 1-D and 2-D, and in gcmx_stage, gcmx_step_faces
+ * and gcmx_step_face_map, the generic per-stage kernel with identical results.
  *
  * Non-finite input: the parity bars hold for finite states.
  * The limiter is built from v_min_f64 / v_max_f64, which return the operand
@@ -177,7 +222,9 @@ gcmx_status gcmx_set_kernel_path(gcmx_ctx* ctx, gcmx_path path);
 gcmx_status gcmx_set_step_schedule(gcmx_ctx* ctx, gcmx_schedule sched, int rows_per_block);
 /* The one-pass step's floating-point build (k_step_tx2 / k_fused_xyz / k_step_ortho; the
  * per-stage kernels always keep the reference's roundings).  Default FMA;
- * environment GCMX_FP=exact makes EXACT the default of new contexts. */
+ * environment GCMX_FP=exact makes EXACT the default of new contexts.  Accepted
+ * on acoustic contexts, where it changes nothing (k_step_acoustic has the one
+ * exact build). */
 gcmx_status gcmx_set_fp_mode(gcmx_ctx* ctx, gcmx_fp_mode mode);
 gcmx_status gcmx_get_fp_mode(const gcmx_ctx* ctx, gcmx_fp_mode* mode);
 /* Which path gcmx_step would take now (after materials are set). */
