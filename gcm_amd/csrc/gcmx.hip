@@ -21,10 +21,12 @@
 #include "launch.hpp"
 #include "ortho.hpp"
 #include "acoustic.hpp"
+#include "plan.hpp"
 
 using namespace gcmx;
 static_assert(GCMX_MAX_BORDER_Q == kMaxBorderQ, "border quantity limit");
 static_assert(GCMX_MAX_FACE_CONDITIONS == kMaxFaceConds && GCMX_NO_FACE_CONDITION == kNoFaceCond, "face maps");
+static_assert(kPlanHetMaxMaterials == kHetMaxMaterials, "plan.hpp restates the HET material limit");
 
 namespace {
 
@@ -144,24 +146,15 @@ struct gcmx_ctx {
 	int max_mat_id = -1;           // largest id in mat_d (set_materials must cover it)
 	AxisTable* tabs_d = nullptr;   // [mat][D]
 	double tabs_tau = NAN;
-	bool iso_fast = false;         // fast kernels admissible (3-D, homogeneous, iso structure)
-	bool iso2_fast = false;        // the 2-D one-pass step may run its isotropic kernel
-	IsoAxis iso[3] = {};           // per-axis values for the fast kernels (tau part in build_tables)
-	bool iso_het = false;          // per-node materials, every material of the iso structure (k_step_tx2 HET)
-	bool het_ok = false;           // this tau: floor(q) = 0 and equal axes for every material
-	std::vector<IsoAxis> het_iso;  // [mat]: tau-independent part (axis 0)
-	IsoAxis* het_d = nullptr;      // [mat] on the device, per tau
-	bool ortho_fast = false;       // 3-D, homogeneous, unrotated orthotropic structure (k_step_ortho)
-	bool ortho_ok = false;         // this tau: every pair's feet lie on the sides the kernel reads
-	OrthoAxis ortho[3] = {};       // per-axis values (tau part in build_tables)
-	bool ortho_het = false;        // per-node materials, every material of the orthotropic structure (k_step_ortho HET)
-	bool ortho_het_ok = false;     // this tau: every material's feet on the sides the kernel reads, floor(q) = 0
-	std::vector<OrthoAxis> ortho_het_h;  // [mat][3]: per-axis values (tau part in build_tables)
+	Medium medium = Medium::General;  // set by refresh_fast: what the matrices' structure admits
+	bool tau_ok = true;            // set by build_tables: this tau's feet lie where that medium's one-pass kernel reads them
+	IsoAxis iso[3] = {};           // Iso3 / Iso2: per-axis values for the fast kernels (tau part in build_tables)
+	IsoAxis* het_d = nullptr;      // IsoHet: [mat] on the device, per tau
+	OrthoAxis ortho[3] = {};       // Ortho: per-axis values (tau part in build_tables)
+	std::vector<OrthoAxis> ortho_het_h;  // OrthoHet: [mat][3] per-axis values (tau part in build_tables)
 	OrthoAxis* ortho_het_d = nullptr;    // [mat][3] on the device, per tau
 	gcmx_model model = GCMX_MODEL_ELASTIC;  // what the PDE vector holds (gcmx_create_model)
-	bool ac_fast = false;          // acoustic context, one material, no ids, the acoustic structure
-	bool ac_ok = false;            // this tau: each axis's two feet on the sides k_step_acoustic reads, q != 0
-	AcAxis ac[3] = {};             // per-axis values (tau part in build_tables)
+	AcAxis ac[3] = {};             // Acoustic: per-axis values (tau part in build_tables)
 	bool ghosts_touched = false;   // node-list border fills / contact copies / ghost uploads happened
 	bool last_ode_fused = false;   // the last gcmx_step_ode scaled the stresses in the step's epilogue
 	unsigned faces_written = 0;    // faces (bit 2*axis + side) whose ghosts a face fill wrote
@@ -301,6 +294,40 @@ gcmx_status check_ctx(gcmx_ctx* c) {
 	return GCMX_OK;
 }
 
+// The per-tau part of an IsoAxis from one axis's table: feet k and k^1 share q,
+// feet 2..nfeet-1 (3-D: 6 feet, 2-D: 4) share q (|L| equal, checked at
+// extraction).  False: the feet are not consistent.
+bool fill_iso_axis(const AxisTable& t, int bs, int nfeet, IsoAxis& A) {
+	for (int k = 1; k < nfeet; k++) {
+		const int ref = (k < 2) ? 0 : 2;
+		if (t.kf[k] != t.kf[ref] || std::memcmp(t.coef[k], t.coef[ref], sizeof(t.coef[k])) != 0) return false;
+	}
+	for (int i = 0; i < 3; i++) {
+		A.c1[i] = i < bs ? t.coef[0][i] : 0.0;
+		A.c2[i] = i < bs ? t.coef[2][i] : 0.0;
+	}
+	A.kf1 = t.kf[0];
+	A.kf2 = t.kf[2];
+	lagrange_weights(A.c1, A.kf1 == 0 ? bs : 0, A.w1);
+	lagrange_weights(A.c2, A.kf2 == 0 ? bs : 0, A.w2);
+	return true;
+}
+
+// The per-tau part of an OrthoAxis: per pair p the feet 2p (+s side) and 2p+1
+// (-s side) share q.  False: they do not.  `sides_ok` is cleared when a pair's
+// feet lie elsewhere (tau <= 0) or on the node (q = 0).
+bool fill_ortho_axis(const AxisTable& t, int bs, OrthoAxis& A, bool& sides_ok) {
+	for (int p = 0; p < 3; p++) {
+		const int k = 2 * p;
+		if (t.kf[k] != t.kf[k + 1] || std::memcmp(t.coef[k], t.coef[k + 1], sizeof(t.coef[k])) != 0) return false;
+		if (t.shift[k] != 1 || t.shift[k + 1] != -1 || t.zero_q[k] || t.zero_q[k + 1]) sides_ok = false;
+		for (int i = 0; i < 3; i++) A.c[p][i] = i < bs ? t.coef[k][i] : 0.0;
+		A.kf[p] = t.kf[k];
+		lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
+	}
+	return true;
+}
+
 // Per-tau tables: crossingPoints (GridCharacteristicMethod.hpp:56-59), q = |dx|/h
 // (:84), k = floor(q) with the reference's interpolation assertions
 // (EqualDistanceLineInterpolator.hpp:20-23) and the Newton coefficients (:58-66).
@@ -339,121 +366,77 @@ gcmx_status build_tables(gcmx_ctx* c, double tau) {
 				for (int i = 1; i <= bs; i++) t.coef[k][i - 1] = ((q - i) + 1) / i;
 			}
 		}
-	if (c->iso_fast || c->iso2_fast) {
-		const int nfeet = D == 3 ? 6 : 4;
-		for (int s = 0; s < D; s++) {
-			const AxisTable& t = h[s];
-			IsoAxis& A = c->iso[s];
-			// feet k and k^1 share q; feet 2..5 (2-D: 2, 3) share q (|L| equal, checked at extraction)
-			for (int k = 1; k < nfeet; k++) {
-				const int ref = (k < 2) ? 0 : 2;
-				if (t.kf[k] != t.kf[ref] || std::memcmp(t.coef[k], t.coef[ref], sizeof(t.coef[k])) != 0)
-					return fail(GCMX_ERR_STATE, "inconsistent foot data");
-			}
-			for (int i = 0; i < 3; i++) {
-				A.c1[i] = i < bs ? t.coef[0][i] : 0.0;
-				A.c2[i] = i < bs ? t.coef[2][i] : 0.0;
-			}
-			A.kf1 = t.kf[0];
-			A.kf2 = t.kf[2];
-			lagrange_weights(A.c1, A.kf1 == 0 ? bs : 0, A.w1);
-			lagrange_weights(A.c2, A.kf2 == 0 ? bs : 0, A.w2);
-		}
-	}
-	if (c->ortho_fast) {
-		// per pair p the feet 2p (+s side) and 2p+1 (-s side) share q; a step that
-		// puts them elsewhere (tau <= 0) takes the generic stages
-		c->ortho_ok = true;
-		for (int s = 0; s < D; s++) {
-			const AxisTable& t = h[s];
-			OrthoAxis& A = c->ortho[s];
-			for (int p = 0; p < 3; p++) {
-				const int k = 2 * p;
-				if (t.kf[k] != t.kf[k + 1] || std::memcmp(t.coef[k], t.coef[k + 1], sizeof(t.coef[k])) != 0)
-					return fail(GCMX_ERR_STATE, "inconsistent foot data");
-				if (t.shift[k] != 1 || t.shift[k + 1] != -1 || t.zero_q[k] || t.zero_q[k + 1]) c->ortho_ok = false;
-				for (int i = 0; i < 3; i++) A.c[p][i] = i < bs ? t.coef[k][i] : 0.0;
-				A.kf[p] = t.kf[k];
-				lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
-			}
-		}
-	}
-	if (c->ac_fast) {
+	const char* inconsistent = "inconsistent foot data";
+	std::vector<IsoAxis> ht;  // IsoHet: lives until the stream is synchronised below
+	switch (c->medium) {
+	case Medium::General: break;
+	case Medium::Iso3:
+	case Medium::Iso2:
+		for (int s = 0; s < D; s++)
+			if (!fill_iso_axis(h[s], bs, D == 3 ? 6 : 4, c->iso[s])) return fail(GCMX_ERR_STATE, inconsistent);
+		break;
+	case Medium::Ortho:
+		// a step that puts a pair's feet elsewhere (tau <= 0) takes the generic stages
+		c->tau_ok = true;
+		for (int s = 0; s < D; s++)
+			if (!fill_ortho_axis(h[s], bs, c->ortho[s], c->tau_ok)) return fail(GCMX_ERR_STATE, inconsistent);
+		break;
+	case Medium::Acoustic:
 		// rows 0 (L = +c: foot on the -s side) and 1 (+s side) share q; a step that
 		// puts them elsewhere (tau <= 0) or on the node (q = 0) takes the generic stages
-		c->ac_ok = true;
+		c->tau_ok = true;
 		for (int s = 0; s < D; s++) {
 			const AxisTable& t = h[s];
 			AcAxis& A = c->ac[s];
 			if (t.kf[0] != t.kf[1] || std::memcmp(t.coef[0], t.coef[1], sizeof(t.coef[0])) != 0)
-				return fail(GCMX_ERR_STATE, "inconsistent foot data");
-			if (t.shift[0] != -1 || t.shift[1] != 1 || t.zero_q[0] || t.zero_q[1]) c->ac_ok = false;
+				return fail(GCMX_ERR_STATE, inconsistent);
+			if (t.shift[0] != -1 || t.shift[1] != 1 || t.zero_q[0] || t.zero_q[1]) c->tau_ok = false;
 			for (int i = 0; i < 3; i++) A.c[i] = i < bs ? t.coef[0][i] : 0.0;
 			A.kf = t.kf[0];
 		}
-	}
-	if (c->ortho_het) {
-		// one OrthoAxis[3] per material, filled as the homogeneous branch fills its
-		// three; the one-pass step also needs floor(q) = 0 for every pair (KF0 only)
-		c->ortho_het_ok = true;
+		break;
+	case Medium::OrthoHet:
+		// one OrthoAxis[3] per material; the one-pass step also needs floor(q) = 0
+		// for every pair (KF0 only)
+		c->tau_ok = true;
 		for (int m = 0; m < c->n_mat; m++)
 			for (int s = 0; s < D; s++) {
-				const AxisTable& t = h[(size_t)m * D + s];
 				OrthoAxis& A = c->ortho_het_h[(size_t)m * 3 + s];
-				for (int p = 0; p < 3; p++) {
-					const int k = 2 * p;
-					if (t.kf[k] != t.kf[k + 1] || std::memcmp(t.coef[k], t.coef[k + 1], sizeof(t.coef[k])) != 0)
-						return fail(GCMX_ERR_STATE, "inconsistent foot data");
-					if (t.shift[k] != 1 || t.shift[k + 1] != -1 || t.zero_q[k] || t.zero_q[k + 1] || t.kf[k] != 0)
-						c->ortho_het_ok = false;
-					for (int i = 0; i < 3; i++) A.c[p][i] = i < bs ? t.coef[k][i] : 0.0;
-					A.kf[p] = t.kf[k];
-					lagrange_weights(A.c[p], A.kf[p] == 0 ? bs : 0, A.w[p]);
-				}
+				if (!fill_ortho_axis(h[(size_t)m * D + s], bs, A, c->tau_ok)) return fail(GCMX_ERR_STATE, inconsistent);
+				if (A.kf[0] != 0 || A.kf[1] != 0 || A.kf[2] != 0) c->tau_ok = false;
 			}
-		if (c->ortho_het_ok) {  // the host copy lives in the context; synchronised below
+		if (c->tau_ok) {  // the host copy lives in the context; synchronised below
 			if (!c->ortho_het_d) HIP_TRY(hipMalloc(&c->ortho_het_d, (size_t)kHetMaxMaterials * 3 * sizeof(OrthoAxis)));
 			HIP_TRY(hipMemcpyAsync(c->ortho_het_d, c->ortho_het_h.data(), c->ortho_het_h.size() * sizeof(OrthoAxis),
 			                       hipMemcpyHostToDevice, c->stream));
 		}
-	}
-	HIP_TRY(hipMemcpyAsync(c->tabs_d, h.data(), h.size() * sizeof(AxisTable),
-	                       hipMemcpyHostToDevice, c->stream));
-	if (c->iso_het) {
+		break;
+	case Medium::IsoHet: {
 		// one IsoAxis per material for all three stages: the axes' tables must be
-		// bitwise equal (equal h) and every foot in [node, node + 1) (floor(q) = 0)
-		std::vector<IsoAxis> ht(c->n_mat);
+		// bitwise equal (equal h) and every foot in [node, node + 1) (floor(q) = 0);
+		// inconsistent feet take the generic stages too
+		ht.resize(c->n_mat);
 		bool ok = true;
 		for (int m = 0; m < c->n_mat && ok; m++) {
 			IsoAxis A[3];
-			for (int s = 0; s < 3 && ok; s++) {
-				const AxisTable& t = h[(size_t)m * D + s];
+			for (int s = 0; s < 3 && ok; s++)
 				ok = iso_axis_extract(s, &c->U[((size_t)m * D + s) * M * M], &c->U1[((size_t)m * D + s) * M * M],
-				                      &c->L[((size_t)m * D + s) * M], A[s]);
-				for (int k = 1; k < 6 && ok; k++) {
-					const int ref = (k < 2) ? 0 : 2;
-					ok = t.kf[k] == t.kf[ref] && std::memcmp(t.coef[k], t.coef[ref], sizeof(t.coef[k])) == 0;
-				}
-				for (int i = 0; i < 3; i++) {
-					A[s].c1[i] = i < bs ? t.coef[0][i] : 0.0;
-					A[s].c2[i] = i < bs ? t.coef[2][i] : 0.0;
-				}
-				A[s].kf1 = t.kf[0];
-				A[s].kf2 = t.kf[2];
-				lagrange_weights(A[s].c1, A[s].kf1 == 0 ? bs : 0, A[s].w1);
-				lagrange_weights(A[s].c2, A[s].kf2 == 0 ? bs : 0, A[s].w2);
-				ok = ok && A[s].kf1 == 0 && A[s].kf2 == 0;
-			}
+				                      &c->L[((size_t)m * D + s) * M], A[s]) &&
+				     fill_iso_axis(h[(size_t)m * D + s], bs, 6, A[s]) && A[s].kf1 == 0 && A[s].kf2 == 0;
 			ok = ok && std::memcmp(&A[0], &A[1], sizeof(IsoAxis)) == 0 && std::memcmp(&A[0], &A[2], sizeof(IsoAxis)) == 0;
 			ht[m] = A[0];
 		}
-		c->het_ok = ok;
+		c->tau_ok = ok;
 		if (ok) {
 			if (!c->het_d) HIP_TRY(hipMalloc(&c->het_d, 256 * sizeof(IsoAxis)));
 			HIP_TRY(hipMemcpyAsync(c->het_d, ht.data(), ht.size() * sizeof(IsoAxis), hipMemcpyHostToDevice,
 			                       c->stream));
 		}
+		break;
 	}
+	}
+	HIP_TRY(hipMemcpyAsync(c->tabs_d, h.data(), h.size() * sizeof(AxisTable),
+	                       hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->tabs_tau = tau;
 	return GCMX_OK;
@@ -916,115 +899,101 @@ bool gcmx::acoustic_axis_extract(int D, int s, const double* U, const double* U1
 
 namespace {
 
-// Fast kernels: 3-D, one material, no per-node ids, isotropic zero pattern.
-void refresh_fast(gcmx_ctx* c) {
+// Which structure the matrices have (c->medium): the first of the patterns
+// below that every material and axis matches.  tau_ok starts true except on
+// the per-node media, whose feet are only known once a step built its tables.
+Medium recognise_medium(gcmx_ctx* c) {
 	const int D = c->D, M = c->M;
+	// extract(s, U, U1, L, m) for every axis of the first n materials
+	auto every = [&](int n, auto extract) {
+		for (int m = 0; m < n; m++)
+			for (int s = 0; s < D; s++) {
+				const size_t i = (size_t)m * D + s;
+				if (!extract(s, &c->U[i * M * M], &c->U1[i * M * M], &c->L[i * M], m)) return false;
+			}
+		return true;
+	};
+	const bool one = c->mat_d == nullptr && c->n_mat == 1;  // one material, no per-node ids
+	const bool ids = c->mat_d != nullptr && c->n_mat >= 1 && c->n_mat <= kHetMaxMaterials;
+	c->ortho_het_h.clear();
 	if (c->model == GCMX_MODEL_ACOUSTIC) {
-		// the elastic patterns index 9 (5) columns: none is tried.  One material
-		// without per-node ids of the acoustic pattern: structure 3, and in 3-D the
-		// one-pass step where the layout admits it (effective_path)
-		c->iso_fast = c->iso2_fast = c->iso_het = c->het_ok = false;
-		c->ortho_fast = c->ortho_ok = c->ortho_het = c->ortho_het_ok = false;
-		bool ac = c->mat_d == nullptr && c->n_mat == 1;
-		for (int sx = 0; ac && sx < D; sx++)
-			ac = acoustic_axis_extract(D, sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M],
-			                           &c->L[(size_t)sx * M], c->ac[sx]);
-		c->ac_fast = ac;
-		c->ac_ok = ac;
-		c->tabs_tau = NAN;
-		return;
+		// the elastic patterns index 9 (5) columns: none is tried
+		const bool ac = one && every(1, [&](int s, const double* U, const double* U1, const double* L, int) {
+			                return acoustic_axis_extract(D, s, U, U1, L, c->ac[s]);
+		                });
+		return ac ? Medium::Acoustic : Medium::General;
 	}
-	bool fits = (D == 3) && (c->mat_d == nullptr) && (c->n_mat == 1) && onepass_layout_ok(c->geo);
-	for (int sx = 0; fits && sx < D; sx++)
-		fits = iso_axis_extract(sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M],
-		                        &c->L[(size_t)sx * M], c->iso[sx]);
-	c->iso_fast = fits;
-	// the 2-D one-pass step's isotropic kernel: one material, the ElasticModel<2> structure
-	bool fits2 = D == 2 && c->mat_d == nullptr && c->n_mat == 1 && step2d_iso_supported(c->geo);
-	for (int sx = 0; fits2 && sx < D; sx++)
-		fits2 = iso2_axis_extract(sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M], &c->L[(size_t)sx * M],
-		                          c->iso[sx]);
-	c->iso2_fast = fits2;
+	if (D == 3 && one && onepass_layout_ok(c->geo) &&
+	    every(1, [&](int s, const double* U, const double* U1, const double* L, int) {
+		    return iso_axis_extract(s, U, U1, L, c->iso[s]);
+	    }))
+		return Medium::Iso3;
+	// the 2-D one-pass step's isotropic kernel: the ElasticModel<2> structure
+	if (D == 2 && one && step2d_iso_supported(c->geo) &&
+	    every(1, [&](int s, const double* U, const double* U1, const double* L, int) {
+		    return iso2_axis_extract(s, U, U1, L, c->iso[s]);
+	    }))
+		return Medium::Iso2;
 	// heterogeneous one-pass step: per-node ids and every material of the structure
-	bool het = !fits && D == 3 && c->mat_d != nullptr && c->n_mat >= 1 && c->n_mat <= kHetMaxMaterials &&
-	           onepass_layout_ok(c->geo) && het_supported(c->geo);
-	for (int m = 0; het && m < c->n_mat; m++)
-		for (int sx = 0; het && sx < D; sx++) {
-			IsoAxis tmp{};
-			het = iso_axis_extract(sx, &c->U[((size_t)m * D + sx) * M * M], &c->U1[((size_t)m * D + sx) * M * M],
-			                       &c->L[((size_t)m * D + sx) * M], tmp);
-		}
-	c->iso_het = het;
-	c->het_ok = false;
+	if (D == 3 && ids && onepass_layout_ok(c->geo) && het_supported(c->geo) &&
+	    every(c->n_mat, [&](int s, const double* U, const double* U1, const double* L, int) {
+		    IsoAxis tmp{};
+		    return iso_axis_extract(s, U, U1, L, tmp);
+	    }))
+		return Medium::IsoHet;
 	// the orthotropic one-pass step: tried only when the isotropic pattern failed
 	// (isotropic matrices never match it: their row order differs)
-	bool ortho = !fits && D == 3 && c->mat_d == nullptr && c->n_mat == 1 && onepass_layout_ok(c->geo);
-	for (int sx = 0; ortho && sx < D; sx++)
-		ortho = ortho_axis_extract(sx, &c->U[(size_t)sx * M * M], &c->U1[(size_t)sx * M * M], &c->L[(size_t)sx * M],
-		                           c->ortho[sx]);
-	c->ortho_fast = ortho;
-	c->ortho_ok = ortho;
+	if (D == 3 && one && onepass_layout_ok(c->geo) &&
+	    every(1, [&](int s, const double* U, const double* U1, const double* L, int) {
+		    return ortho_axis_extract(s, U, U1, L, c->ortho[s]);
+	    }))
+		return Medium::Ortho;
 	// the same with per-node ids: every material of the orthotropic structure (a
 	// set that mixes it with isotropic-pattern materials stays general)
-	bool ohet = !het && D == 3 && c->mat_d != nullptr && c->n_mat >= 1 && c->n_mat <= kHetMaxMaterials &&
-	            onepass_layout_ok(c->geo);
-	c->ortho_het_h.assign(ohet ? (size_t)c->n_mat * 3 : 0, OrthoAxis{});
-	for (int m = 0; ohet && m < c->n_mat; m++)
-		for (int sx = 0; ohet && sx < D; sx++)
-			ohet = ortho_axis_extract(sx, &c->U[((size_t)m * D + sx) * M * M], &c->U1[((size_t)m * D + sx) * M * M],
-			                          &c->L[((size_t)m * D + sx) * M], c->ortho_het_h[(size_t)m * 3 + sx]);
-	c->ortho_het = ohet;
-	c->ortho_het_ok = false;
+	if (D == 3 && ids && onepass_layout_ok(c->geo)) {
+		c->ortho_het_h.assign((size_t)c->n_mat * 3, OrthoAxis{});
+		if (every(c->n_mat, [&](int s, const double* U, const double* U1, const double* L, int m) {
+			    return ortho_axis_extract(s, U, U1, L, c->ortho_het_h[(size_t)m * 3 + s]);
+		    }))
+			return Medium::OrthoHet;
+	}
+	return Medium::General;
+}
+
+void refresh_fast(gcmx_ctx* c) {
+	c->medium = recognise_medium(c);
+	c->tau_ok = c->medium != Medium::IsoHet && c->medium != Medium::OrthoHet;
 	c->tabs_tau = NAN;
 }
 
-// The one-pass 2-D step (k_step2d) runs where its preconditions hold: one
-// material, no ghost ever written (so every ghost of both layers is zero and
-// the two layers' ghosts agree, whichever one the step leaves the state in),
-// no X-slab exchange, a borderSize it is built for, and no forced per-stage path.
-bool step2d_admissible(const gcmx_ctx* c) {
-	return c->D == 2 && c->model == GCMX_MODEL_ELASTIC && step2d_supported(c->geo) && c->mat_d == nullptr && c->n_mat == 1 && !c->ghosts_touched &&
-	       c->faces_written == 0 && !has_halo(c) && c->path != GCMX_PATH_GENERIC && c->path != GCMX_PATH_SPLIT;
-}
-// The same with whole-face border conditions `on` (bit 2*axis + side): the
-// isotropic kernel, the y ghost columns formed in the pass from the mirrored
-// inner columns (Y >= bs + 1), and every face whose ghosts an earlier step wrote
-// refreshed now.
-bool step2d_faces_admissible(const gcmx_ctx* c, unsigned on) {
-	return c->D == 2 && c->iso2_fast && step2d_iso_supported(c->geo) && c->mat_d == nullptr && c->n_mat == 1 &&
-	       !c->ghosts_touched && (c->faces_written & ~on) == 0 && !has_halo(c) && c->path != GCMX_PATH_GENERIC &&
-	       c->path != GCMX_PATH_SPLIT && c->geo.sizes[1] >= c->bs + 1;
-}
-
-gcmx_path effective_path(gcmx_ctx* c) {
-	if (c->model == GCMX_MODEL_ACOUSTIC) {  // the one-pass acoustic step (3-D) or the generic stages
-		const bool onepass = c->D == 3 && c->ac_fast && c->ac_ok && c->bs <= 3 && acoustic_supported(c->geo) &&
-		                     !c->ghosts_touched && c->faces_written == 0 && !has_halo(c) &&
-		                     (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
-		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
-	}
-	if (c->iso_het) {  // per-node materials: the one-pass step or the generic stages
-		if (c->path == GCMX_PATH_GENERIC || c->path == GCMX_PATH_SPLIT || c->ghosts_touched) return GCMX_PATH_GENERIC;
-		return GCMX_PATH_FUSED;
-	}
-	if (c->D == 2) return step2d_admissible(c) ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
-	if (c->ortho_het) {  // per-node orthotropic materials: the homogeneous step's conditions, the HET instance set
-		const bool onepass = c->bs <= 3 && ortho_het_supported(c->geo) && !c->ghosts_touched && c->faces_written == 0 &&
-		                     (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
-		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
-	}
-	if (c->ortho_fast) {  // the one-pass orthotropic step or the generic stages
-		const bool onepass = c->ortho_ok && c->bs <= 3 && ortho_supported(c->geo) && !c->ghosts_touched &&
-		                     c->faces_written == 0 && (c->path == GCMX_PATH_AUTO || c->path == GCMX_PATH_FUSED);
-		return onepass ? GCMX_PATH_FUSED : GCMX_PATH_GENERIC;
-	}
-	if (c->D != 3 || !c->iso_fast || c->bs > 3) return GCMX_PATH_GENERIC;
-	if (c->path == GCMX_PATH_GENERIC) return GCMX_PATH_GENERIC;
-	// the per-stage kernels address whole layers with 32-bit offsets
-	const gcmx_path split = fast_layout_ok(c->geo) ? GCMX_PATH_SPLIT : GCMX_PATH_GENERIC;
-	if (c->path == GCMX_PATH_SPLIT) return split;
-	if (c->ghosts_touched || !fused_supported(c->geo)) return split;
-	return GCMX_PATH_FUSED;
+// Everything the step planner reads (plan.hpp), from the context as it stands.
+PlanFacts facts_of(const gcmx_ctx* c) {
+	const Geo& g = c->geo;
+	PlanFacts f{};
+	f.D = c->D;
+	f.bs = c->bs;
+	f.Y = g.sizes[1];
+	f.Z = g.sizes[2];
+	f.n_mat = c->n_mat;
+	f.model = c->model;
+	f.medium = c->medium;
+	f.tau_ok = c->tau_ok;
+	f.has_ids = c->mat_d != nullptr;
+	f.path = c->path;
+	f.ghosts_touched = c->ghosts_touched;
+	f.faces_written = c->faces_written;
+	f.has_halo = has_halo(c);
+	f.fused_supported = fused_supported(g);
+	f.fused_faces_supported = fused_faces_supported(g);
+	f.zs_admissible = c->medium == Medium::Iso3 && zs_admissible(g, c->iso);
+	f.het_supported = het_supported(g);
+	f.ortho_supported = ortho_supported(g);
+	f.ortho_het_supported = ortho_het_supported(g);
+	f.acoustic_supported = acoustic_supported(g);
+	f.step2d_supported = step2d_supported(g);
+	f.step2d_iso_supported = step2d_iso_supported(g);
+	f.fast_layout_ok = fast_layout_ok(g);
+	return f;
 }
 
 double node_stage_bytes(const gcmx_ctx* c) { return 2.0 * c->M * sizeof(double); }
@@ -1078,10 +1047,7 @@ gcmx_status stage_impl(gcmx_ctx* c, int axis, double tau) {
 	}
 	const Geo& g = c->geo;
 	const double bytes = node_stage_bytes(c) * (double)g.n_inner;
-	// no per-stage het kernels; the per-stage kernels of the split path are 3-D only
-	const gcmx_path p =
-	    (c->model == GCMX_MODEL_ACOUSTIC || c->iso_het || c->ortho_fast || c->ortho_het || c->D != 3 || !fast_layout_ok(c->geo)) ? GCMX_PATH_GENERIC
-	                                                                                          : effective_path(c);
+	const gcmx_path p = plan_stage_path(facts_of(c));
 	bool ok;
 	if (p == GCMX_PATH_GENERIC) {
 		Timed t(c, "stage_generic", bytes, c->stream);
@@ -1100,7 +1066,7 @@ gcmx_status stage_impl(gcmx_ctx* c, int axis, double tau) {
 	HIP_TRY(hipGetLastError());
 	std::swap(c->cur, c->nxt);
 	touch_layer(c);
-	c->last_path = p == GCMX_PATH_GENERIC ? GCMX_PATH_GENERIC : GCMX_PATH_SPLIT;
+	c->last_path = p;
 	return GCMX_OK;
 }
 
@@ -1685,12 +1651,16 @@ struct SlabJoin {
 	}
 };
 
-// One 2-D step in one pass (k_step2d, cur -> nxt, then swap): the caller
-// checked step2d_admissible.
-gcmx_status step2d(gcmx_ctx* c, const Face2* faces = nullptr) {
+}  // extern "C"
+
+namespace {
+
+// One 2-D step in one pass (k_step2d, cur -> nxt, then swap): plan_step chose it.
+gcmx_status step2d(gcmx_ctx* c, const Face2* faces) {
 	const Geo& g = c->geo;
 	Timed t(c, "step2d", node_stage_bytes(c) * (double)g.n_inner, c->stream);
-	if (!launch_step2d(c->cur, c->nxt, g, c->tabs_d, c->iso2_fast ? c->iso : nullptr, c->stream, &t.kname, faces))
+	if (!launch_step2d(c->cur, c->nxt, g, c->tabs_d, c->medium == Medium::Iso2 ? c->iso : nullptr, c->stream, &t.kname,
+	                   faces))
 		return fail(GCMX_ERR_UNSUPPORTED, "no 2-D step variant for this configuration");
 	HIP_TRY(hipGetLastError());
 	std::swap(c->cur, c->nxt);
@@ -1699,8 +1669,9 @@ gcmx_status step2d(gcmx_ctx* c, const Face2* faces = nullptr) {
 	return GCMX_OK;
 }
 
-// One fused step (k_step_tx2 / k_fused_xyz): the caller checked the path.
-// `fb`: y/z face conditions (x faces already filled in memory), or null.
+// One one-pass step of the family plan_step chose (`kind`: Tx2, Ortho or Acoustic).
+// `fb`: y/z face conditions (x faces already filled in memory) and the folded
+// ODE, or null; k_step_tx2 / k_fused_xyz only.
 // `final`: the step's result is the new state (no separate ODE pass follows).
 // Only then may the boundary-first / X-slab schedules post the exchange of the
 // new boundary planes inside the step (step_posted); otherwise end_step posts
@@ -1710,8 +1681,10 @@ gcmx_status step2d(gcmx_ctx* c, const Face2* faces = nullptr) {
 // and at the final gcmx_sync (a rank posting a second generation
 // after a non-folded ODE mismatched RCCL's send/recv counts; a rank posting one
 // step later than its neighbour left the last wait unmatched).
-gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
+gcmx_status fused_step(gcmx_ctx* c, StepKind kind, const FaceBC* fb, bool final) {
 	gcmx_status s = GCMX_OK;
+	// k_step_ortho and k_step_acoustic form no faces and fold no ODE
+	if (fb && kind != StepKind::Tx2) return fail(GCMX_ERR_UNSUPPORTED, "fused path launch failed");
 	// One pass per step (k_fused_xyz: cur -> nxt, then swap).  Ghost planes of
 	// `cur` must hold E_n; with the X-slab schedule the exchange of the NEW
 	// boundary planes (E_{n+1}, into the ghost planes of `nxt`) runs while the
@@ -1720,23 +1693,28 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 	const int X = g.sizes[0], bs = c->bs;
 	const double plane_bytes = node_stage_bytes(c) * (double)g.sizes[1] * g.sizes[2];
 	const bool halo = has_halo(c);
-	auto xyz = [&](const char* name, int x0, int x1, hipStream_t st, int rows, int xb0 = 0, int xb1 = 0) {
+	auto xyz = [&](const char* name, int x0, int x1, hipStream_t st, int rows, int xb0 = 0, int xb1 = 0) -> bool {
 		Timed t(c, name, plane_bytes * ((x1 - x0) + (xb1 - xb0)), st);
-		if (c->model == GCMX_MODEL_ACOUSTIC)  // effective_path admitted it: no face conditions, no halo, one range
-			return fb == nullptr && xb1 <= xb0 && launch_step_acoustic(c->cur, c->nxt, g, c->ac, x0, x1, st, rows, &t.kname);
-		if (c->ortho_fast || c->ortho_het) {  // effective_path admitted it: no face conditions, no folded ODE
-			auto launch_o = c->fp_mode == GCMX_FP_EXACT ? ortho_exact::launch_step_ortho : ortho_fma::launch_step_ortho;
+		switch (kind) {
+		case StepKind::Acoustic:  // one plane range: no X slabs, the schedule below is SINGLE
+			return xb1 <= xb0 && launch_step_acoustic(c->cur, c->nxt, g, c->ac, x0, x1, st, rows, &t.kname);
+		case StepKind::Ortho: {
+			auto launch = c->fp_mode == GCMX_FP_EXACT ? ortho_exact::launch_step_ortho : ortho_fma::launch_step_ortho;
 			const OrthoHet ohet{c->ortho_het_d, c->mat_d, c->n_mat, 0};  // this context's own inner nodes' ids
-			return fb == nullptr && launch_o(c->cur, c->nxt, g, c->ortho, x0, x1, st, rows, &t.kname, xb0, xb1,
-			                                 c->ortho_het ? &ohet : nullptr);
+			return launch(c->cur, c->nxt, g, c->ortho, x0, x1, st, rows, &t.kname, xb0, xb1,
+			              c->medium == Medium::OrthoHet ? &ohet : nullptr);
 		}
-		const HetMaterials het{c->het_d, c->mat_d};
-		auto launch = c->fp_mode == GCMX_FP_EXACT ? xyz_exact::launch_fused_xyz : xyz_fma::launch_fused_xyz;
-		return launch(c->cur, c->nxt, g, c->iso, x0, x1, st, rows, fb, &t.kname, c->iso_het ? &het : nullptr,
-		              xb0, xb1);
+		case StepKind::Tx2: {
+			const HetMaterials het{c->het_d, c->mat_d};
+			auto launch = c->fp_mode == GCMX_FP_EXACT ? xyz_exact::launch_fused_xyz : xyz_fma::launch_fused_xyz;
+			return launch(c->cur, c->nxt, g, c->iso, x0, x1, st, rows, fb, &t.kname,
+			              c->medium == Medium::IsoHet ? &het : nullptr, xb0, xb1);
+		}
+		default: return false;  // Stages, Step2d: not a fused_step
+		}
 	};
 	const gcmx_schedule sched =
-	    c->model == GCMX_MODEL_ACOUSTIC ? GCMX_SCHED_SINGLE  // no X slabs: nothing to schedule around
+	    kind == StepKind::Acoustic      ? GCMX_SCHED_SINGLE  // no X slabs: nothing to schedule around
 	    : c->sched == GCMX_SCHED_AUTO   ? (halo ? GCMX_SCHED_BFIRST : GCMX_SCHED_SINGLE)
 	                                    : c->sched;
 	bool ok = true;
@@ -1833,10 +1811,6 @@ gcmx_status fused_step(gcmx_ctx* c, const FaceBC* fb, bool final) {
 	return GCMX_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
 // The Maxwell ODE a step may carry (gcmx_step_ode): one factor per material.
 struct StepOde {
 	bool on = false;
@@ -1854,18 +1828,6 @@ gcmx_status ode_factors(gcmx_ctx* c, double tau, const double* tau0, int n_mat, 
 
 gcmx_status ode_apply(gcmx_ctx* c, const std::vector<double>& f);
 gcmx_status ode_upload(gcmx_ctx* c, const std::vector<double>& f);
-
-// The ODE rides in the one-pass step's store epilogue when the step runs
-// k_step_tx2: over one material (the factor is one number), or over per-node
-// materials on the heterogeneous one-pass step (per-material factors, each
-// node's own read from LDS).  Call after build_tables (het_ok is per tau).
-bool ode_foldable(const gcmx_ctx* c, const StepOde& ode) {
-	// rows longer than 512: only the z split has the store epilogue (uniform medium)
-	if (!ode.on || c->ortho_fast || c->ortho_het || c->bs > 2 || (c->geo.sizes[2] > 512 && !(!c->mat_d && zs_admissible(c->geo, c->iso))))
-		return false;
-	if (!c->mat_d) return ode.f.size() == 1;
-	return c->iso_het && c->het_ok && (int)ode.f.size() <= kHetMaxMaterials;
-}
 
 // Fills fb's ODE fields for a folded ODE (the HET factors uploaded in stream order).
 gcmx_status ode_fold(gcmx_ctx* c, const StepOde& ode, FaceBC& fb) {
@@ -1889,46 +1851,136 @@ gcmx_status end_step(gcmx_ctx* c) {
 	return halo_post(c);
 }
 
-gcmx_status step_body(gcmx_ctx* c, double tau, const StepOde& ode);
+// Where a step's face conditions come from: the six BorderQ of whole faces
+// (gcmx_step_faces), or a face map with its conditions' tables
+// (gcmx_step_face_map); neither for gcmx_step.
+struct FaceSrc {
+	const BorderQ* bq = nullptr;
+	const gcmx_face_map* map = nullptr;
+	const FaceTables* tabs = nullptr;
+};
 
-gcmx_status step_impl(gcmx_ctx* c, double tau, const StepOde& ode) {
-	c->step_posted = false;
-	gcmx_status s = step_body(c, tau, ode);
-	return s ? s : end_step(c);
+// PRESSURE among a condition's quantities (no component of the PDE vector).
+bool sets_pressure(int D, const BorderQ& bq) {
+	for (int k = 0; k < bq.n; k++)
+		if (quantity_comp(D, bq.q[k]) < 0) return true;
+	return false;
 }
 
-gcmx_status step_body(gcmx_ctx* c, double tau, const StepOde& ode) {
+// The ghosts of face f (2*axis + side) written in memory.
+gcmx_status fill_face(gcmx_ctx* c, const FaceSrc& src, int f) {
+	gcmx_status s = halo_wait(c);
+	if (s) return s;
+	Timed t(c, "face_fill", 0.0, c->stream);
+	const int axis = f / 2, side = (f & 1) ? 1 : -1;
+	if (src.map && src.map->map_d[f])
+		launch_face_fill_map(c->cur, c->geo, axis, side, src.map->map_d[f], src.map->bq_d, c->stream);
+	else
+		launch_face_fill(c->cur, c->geo, axis, side, src.map ? src.tabs->bq[src.map->uni[f]] : src.bq[f], c->stream);
+	HIP_TRY(hipGetLastError());
+	c->faces_written |= 1u << f;
+	return GCMX_OK;
+}
+
+// Whole y (and z) faces as the one pass forms them (Face2 / FaceBC): none sets
+// PRESSURE (plan_step).
+template <class F>
+F whole_faces(int D, unsigned on, const BorderQ* bq) {
+	F fb{};
+	for (int f = 2; f < 2 * D; f++) {
+		if (!((on >> f) & 1u)) continue;
+		fb.on |= 1u << (f - 2);
+		for (int k = 0; k < bq[f].n; k++) {
+			const int comp = quantity_comp(D, bq[f].q[k]);
+			fb.mask[f - 2] |= 1u << comp;
+			fb.two_v[f - 2][comp] = 2 * bq[f].v[k];  // the last setting of a component wins
+		}
+	}
+	return fb;
+}
+
+// A face map's y/z faces, formed inside the one-pass step per face node.
+FaceBC map_faces(const gcmx_face_map* m, const FaceTables& t) {
+	FaceBC fb{};
+	for (int f = 2; f < 6; f++)
+		if (m->map_d[f]) {
+			fb.on |= 1u << (f - 2);
+			fb.map[f - 2] = m->map_d[f];
+		} else if (m->uni[f] >= 0) {  // uniform face: the condition as kernel arguments
+			const FaceCond& fc = t.fc[m->uni[f]];
+			fb.on |= 1u << (f - 2);
+			fb.mask[f - 2] = fc.mask;
+			for (int j = 0; j < 9; j++) fb.two_v[f - 2][j] = fc.two_v[j];
+		}
+	fb.conds = m->fc_d;
+	return fb;
+}
+
+// The one executor behind gcmx_step, gcmx_step_faces, gcmx_step_ode and
+// gcmx_step_face_map: the tables, the plan (plan.hpp), the face fills, the
+// launch, the ODE where the pass did not carry it, and one post of the new state.
+gcmx_status run_step(gcmx_ctx* c, double tau, const StepRequest& req, const FaceSrc& src, const StepOde& ode) {
+	c->step_posted = false;
 	gcmx_status s = build_tables(c, tau);
 	if (s) return s;
+	if (src.map) {
+		if ((s = halo_wait(c)) != GCMX_OK) return s;
+		launch_set_face_tables(src.map->bq_d, src.map->fc_d, *src.tabs, c->stream);
+		HIP_TRY(hipGetLastError());
+	}
 	c->last_ode_fused = false;
-	if (c->D == 2 && effective_path(c) == GCMX_PATH_FUSED) {
-		s = step2d(c);
-		if (s) return s;
-		return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
-	}
-	if (effective_path(c) != GCMX_PATH_FUSED || c->faces_written != 0 || (c->iso_het && !c->het_ok) ||
-	    (c->ortho_het && !c->ortho_het_ok)) {
-		for (int a = 0; a < c->D; a++) {
-			s = stage_impl(c, a, tau);
-			if (s) return s;
-		}
-		return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
-	}
-	if (ode_foldable(c, ode)) {
-		FaceBC fb{};
-		s = ode_fold(c, ode, fb);
-		if (s) return s;
-		s = fused_step(c, &fb, true);
-		if (s) return s;
-		c->last_ode_fused = true;
+	const StepPlan plan = plan_step(facts_of(c), req);
+	const int D = c->D;
+	auto fill = [&](int f0, int f1) -> gcmx_status {
+		for (int f = f0; f < f1; f++)
+			if (((req.on >> f) & 1u) && (s = fill_face(c, src, f)) != GCMX_OK) return s;
 		return GCMX_OK;
+	};
+	if (plan.kind == StepKind::Stages) {
+		for (int a = 0; a < D; a++) {  // BorderConditions::apply(mesh, a), then the stage (Engine.cpp:90-121)
+			if ((s = fill(2 * a, 2 * a + 2)) != GCMX_OK || (s = stage_impl(c, a, tau)) != GCMX_OK) return s;
+		}
+	} else {
+		// x faces in memory, y/z faces formed inside the pass
+		if ((s = fill(0, 2)) != GCMX_OK) return s;
+		if (plan.kind == StepKind::Step2d) {
+			const Face2 f2 = whole_faces<Face2>(D, req.on, src.bq);
+			s = step2d(c, plan.faces_in_pass ? &f2 : nullptr);
+		} else {
+			FaceBC fb{};
+			if (plan.faces_in_pass) fb = src.map ? map_faces(src.map, *src.tabs) : whole_faces<FaceBC>(D, req.on, src.bq);
+			if (plan.ode_folded && (s = ode_fold(c, ode, fb)) != GCMX_OK) return s;
+			// final: no separate ODE pass follows, the step's result is the new state
+			s = fused_step(c, plan.kind, (fb.on || plan.ode_folded) ? &fb : nullptr, !ode.on || plan.ode_folded);
+		}
+		if (s) return s;
 	}
-	s = fused_step(c, nullptr, !ode.on);
-	if (s) return s;
-	return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
+	if (ode.on && !plan.ode_folded && (s = ode_apply(c, ode.f)) != GCMX_OK) return s;
+	c->last_ode_fused = plan.ode_folded;
+	return end_step(c);
 }
 
-gcmx_status step_faces_impl(gcmx_ctx* c, double tau, const gcmx_face* faces, const StepOde& ode);
+// Whole-face conditions (gcmx_step_faces, gcmx_step_ode with faces).
+gcmx_status step_faces_impl(gcmx_ctx* c, double tau, const gcmx_face* faces, const StepOde& ode) {
+	c->last_ode_fused = false;
+	const int D = c->D;
+	BorderQ bq[6] = {};
+	StepRequest req{FaceSource::Faces, 0, false, ode.on, (int)ode.f.size()};
+	for (int f = 0; f < 2 * D; f++) {
+		if (!faces[f].enabled) continue;
+		gcmx_status s = border_q(c, faces[f].n_quantities, faces[f].quantities, faces[f].values, bq[f]);
+		if (s) return s;
+		req.on |= 1u << f;
+		if (f >= 2 && sets_pressure(D, bq[f])) req.yz_pressure = true;
+	}
+	FaceSrc src;
+	src.bq = bq;
+	return run_step(c, tau, req, src, ode);
+}
+
+gcmx_status step_impl(gcmx_ctx* c, double tau, const StepOde& ode) {
+	return run_step(c, tau, StepRequest{FaceSource::None, 0, false, ode.on, (int)ode.f.size()}, FaceSrc{}, ode);
+}
 
 }  // namespace
 
@@ -1961,123 +2013,6 @@ gcmx_status gcmx_step_ode(gcmx_ctx* c, double tau, const gcmx_face* faces, const
 }
 
 int gcmx_last_ode_fused(gcmx_ctx* c) { return c && c->last_ode_fused ? 1 : 0; }
-
-}  // extern "C"
-
-namespace {
-
-gcmx_status step_faces_body(gcmx_ctx* c, double tau, const gcmx_face* faces, const StepOde& ode);
-
-gcmx_status step_faces_impl(gcmx_ctx* c, double tau, const gcmx_face* faces, const StepOde& ode) {
-	c->step_posted = false;
-	gcmx_status s = step_faces_body(c, tau, faces, ode);
-	return s ? s : end_step(c);
-}
-
-gcmx_status step_faces_body(gcmx_ctx* c, double tau, const gcmx_face* faces, const StepOde& ode) {
-	gcmx_status s = GCMX_OK;
-	c->last_ode_fused = false;
-	const int D = c->D;
-	BorderQ bq[6] = {};
-	unsigned on = 0;
-	for (int f = 0; f < 2 * D; f++) {
-		if (!faces[f].enabled) continue;
-		s = border_q(c, faces[f].n_quantities, faces[f].quantities, faces[f].values, bq[f]);
-		if (s) return s;
-		on |= 1u << f;
-	}
-	s = build_tables(c, tau);
-	if (s) return s;
-	auto fill = [&](int f) -> gcmx_status {
-		s = halo_wait(c);
-		if (s) return s;
-		Timed t(c, "face_fill", 0.0, c->stream);
-		launch_face_fill(c->cur, c->geo, f / 2, (f & 1) ? 1 : -1, bq[f], c->stream);
-		HIP_TRY(hipGetLastError());
-		c->faces_written |= 1u << f;
-		return GCMX_OK;
-	};
-	if (D == 2 && step2d_faces_admissible(c, on)) {
-		// One 2-D pass: x faces in memory, y faces formed in the pass (Face2); a
-		// y face with PRESSURE (its trace needs components the pass does not form
-		// at ghosts) keeps the per-stage path.
-		Face2 f2{};
-		bool ok = true;
-		for (int f = 2; f < 4 && ok; f++) {
-			if (!((on >> f) & 1u)) continue;
-			f2.on |= 1u << (f - 2);
-			for (int k = 0; k < bq[f].n; k++) {
-				const int comp = quantity_comp(D, bq[f].q[k]);
-				if (comp < 0) {
-					ok = false;
-					break;
-				}
-				f2.mask[f - 2] |= 1u << comp;
-				f2.two_v[f - 2][comp] = 2 * bq[f].v[k];  // the last setting of a component wins
-			}
-		}
-		if (ok) {
-			for (int f = 0; f < 2; f++)
-				if ((on >> f) & 1u) {
-					s = fill(f);
-					if (s) return s;
-				}
-			s = step2d(c, &f2);
-			if (s) return s;
-			return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
-		}
-	}
-	// One pass: x faces in memory, y/z faces as FaceBC; the y/z faces must be
-	// free of PRESSURE (its trace needs components the fused ghosts do not form)
-	// and no face may hold ghosts written earlier but not refreshed now.
-	bool fused = D == 3 && c->model == GCMX_MODEL_ELASTIC && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
-	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
-	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
-	FaceBC fb{};
-	for (int f = 2; f < 6 && fused; f++) {
-		if (!((on >> f) & 1u)) continue;
-		fb.on |= 1u << (f - 2);
-		for (int k = 0; k < bq[f].n; k++) {
-			const int comp = quantity_comp(D, bq[f].q[k]);
-			if (comp < 0) {
-				fused = false;  // PRESSURE
-				break;
-			}
-			fb.mask[f - 2] |= 1u << comp;
-			fb.two_v[f - 2][comp] = 2 * bq[f].v[k];  // the last setting of a component wins
-		}
-	}
-	if (fused) {
-		for (int f = 0; f < 2; f++)
-			if ((on >> f) & 1u) {
-				s = fill(f);
-				if (s) return s;
-			}
-		const bool fold = ode_foldable(c, ode);
-		if (fold) {
-			s = ode_fold(c, ode, fb);
-			if (s) return s;
-		}
-		s = fused_step(c, (fb.on || fold) ? &fb : nullptr, !(ode.on && !fold));
-		if (s) return s;
-		c->last_ode_fused = fold;
-		return (ode.on && !fold) ? ode_apply(c, ode.f) : GCMX_OK;
-	}
-	for (int a = 0; a < D; a++) {
-		for (int f = 2 * a; f < 2 * a + 2; f++)
-			if ((on >> f) & 1u) {
-				s = fill(f);
-				if (s) return s;
-			}
-		s = stage_impl(c, a, tau);
-		if (s) return s;
-	}
-	return ode.on ? ode_apply(c, ode.f) : GCMX_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 gcmx_status gcmx_face_map_create(gcmx_ctx* c, const uint8_t* const node_condition[6], gcmx_face_map** out) {
 	gcmx_status s = check_ctx(c);
@@ -2128,95 +2063,42 @@ void gcmx_face_map_destroy(gcmx_face_map* m) {
 	delete m;
 }
 
-static gcmx_status step_face_map_body(gcmx_ctx* c, double tau, const gcmx_face_map* m, int n_cond,
-                                      const gcmx_face* conds);
-
 gcmx_status gcmx_step_face_map(gcmx_ctx* c, double tau, const gcmx_face_map* m, int n_cond,
                                const gcmx_face* conds) {
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
-	c->step_posted = false;
-	s = step_face_map_body(c, tau, m, n_cond, conds);
-	return s ? s : end_step(c);
-}
-
-static gcmx_status step_face_map_body(gcmx_ctx* c, double tau, const gcmx_face_map* m, int n_cond,
-                                      const gcmx_face* conds) {
-	gcmx_status s = GCMX_OK;
 	if (!std::isfinite(tau)) return fail(GCMX_ERR_INVALID_ARG, "non-finite time step");
 	if (!m || m->ctx != c) return fail(GCMX_ERR_INVALID_ARG, "face map of another context");
 	if (n_cond < 0 || n_cond > kMaxFaceConds || (n_cond > 0 && !conds))
 		return fail(GCMX_ERR_INVALID_ARG, "0.." + std::to_string(kMaxFaceConds) + " conditions expected");
 	const int D = c->D;
-	unsigned on = 0;
+	StepRequest req{FaceSource::Map, 0, false, false, 0};
 	for (int f = 0; f < 2 * D; f++)
 		if (m->map_d[f] || m->uni[f] >= 0) {
 			if (m->used[f] >> n_cond) return fail(GCMX_ERR_INVALID_ARG, "the face map names a condition not given");
-			on |= 1u << f;
+			req.on |= 1u << f;
 		}
 	FaceTables t{};
 	t.n = n_cond;
-	unsigned pressure = 0;  // conditions that set PRESSURE (the fused ghosts cannot form its trace)
 	for (int k = 0; k < n_cond; k++) {
 		if ((s = border_q(c, conds[k].n_quantities, conds[k].quantities, conds[k].values, t.bq[k])) != GCMX_OK)
 			return s;
 		FaceCond& fc = t.fc[k];
 		for (int q = 0; q < t.bq[k].n; q++) {
 			const int comp = quantity_comp(D, t.bq[k].q[q]);
-			if (comp < 0) {
-				pressure |= 1u << k;
+			if (comp < 0) {  // PRESSURE: no y/z face may use this condition in the pass
+				for (int f = 2; f < 2 * D; f++)
+					if ((m->used[f] >> k) & 1u) req.yz_pressure = true;
 				continue;
 			}
 			fc.mask |= 1u << comp;
 			fc.two_v[comp] = 2 * t.bq[k].v[q];  // the last setting of a component wins
 		}
 	}
-	if ((s = build_tables(c, tau)) != GCMX_OK) return s;
-	if ((s = halo_wait(c)) != GCMX_OK) return s;
-	launch_set_face_tables(m->bq_d, m->fc_d, t, c->stream);
-	HIP_TRY(hipGetLastError());
-	c->last_ode_fused = false;
-	bool fused = D == 3 && c->model == GCMX_MODEL_ELASTIC && !c->ortho_fast && !c->ortho_het && effective_path(c) == GCMX_PATH_FUSED && fused_faces_supported(c->geo) &&
-	             (c->geo.sizes[2] <= 512 || (!c->mat_d && zs_admissible(c->geo, c->iso))) &&
-	             (c->faces_written & ~on) == 0 && (!c->iso_het || c->het_ok);
-	for (int f = 2; f < 2 * D && fused; f++)
-		if (m->used[f] & pressure) fused = false;
-	auto fill = [&](int f) -> gcmx_status {
-		gcmx_status st = halo_wait(c);
-		if (st) return st;
-		Timed tm(c, "face_fill", 0.0, c->stream);
-		if (m->map_d[f])
-			launch_face_fill_map(c->cur, c->geo, f / 2, (f & 1) ? 1 : -1, m->map_d[f], m->bq_d, c->stream);
-		else
-			launch_face_fill(c->cur, c->geo, f / 2, (f & 1) ? 1 : -1, t.bq[m->uni[f]], c->stream);
-		HIP_TRY(hipGetLastError());
-		c->faces_written |= 1u << f;
-		return GCMX_OK;
-	};
-	if (fused) {
-		// x faces in memory, y/z faces formed inside the one-pass step per face node
-		for (int f = 0; f < 2; f++)
-			if (((on >> f) & 1u) && (s = fill(f)) != GCMX_OK) return s;
-		FaceBC fb{};
-		for (int f = 2; f < 6; f++)
-			if (m->map_d[f]) {
-				fb.on |= 1u << (f - 2);
-				fb.map[f - 2] = m->map_d[f];
-			} else if (m->uni[f] >= 0) {  // uniform face: the condition as kernel arguments
-				const FaceCond& fc = t.fc[m->uni[f]];
-				fb.on |= 1u << (f - 2);
-				fb.mask[f - 2] = fc.mask;
-				for (int j = 0; j < 9; j++) fb.two_v[f - 2][j] = fc.two_v[j];
-			}
-		fb.conds = m->fc_d;
-		return fused_step(c, fb.on ? &fb : nullptr, true);
-	}
-	for (int a = 0; a < D; a++) {  // BorderConditions::apply(mesh, a), then the stage (Engine.cpp:90-121)
-		for (int f = 2 * a; f < 2 * a + 2; f++)
-			if (((on >> f) & 1u) && (s = fill(f)) != GCMX_OK) return s;
-		if ((s = stage_impl(c, a, tau)) != GCMX_OK) return s;
-	}
-	return GCMX_OK;
+	FaceSrc src;
+	src.map = m;
+	src.tabs = &t;
+	return run_step(c, tau, req, src, StepOde{});
 }
 
 gcmx_status gcmx_set_fp_mode(gcmx_ctx* c, gcmx_fp_mode mode) {
@@ -2253,11 +2135,19 @@ gcmx_status gcmx_set_kernel_path(gcmx_ctx* c, gcmx_path p) {
 
 int gcmx_matrix_structure(gcmx_ctx* c) {
 	if (!c || c->n_mat <= 0) return 0;
-	if (c->model == GCMX_MODEL_ACOUSTIC) return c->ac_fast ? 3 : 0;
-	return (c->iso_fast || c->iso2_fast || c->iso_het) ? 1 : (c->ortho_fast || c->ortho_het) ? 2 : 0;
+	switch (c->medium) {
+	case Medium::General: return 0;
+	case Medium::Iso3:
+	case Medium::Iso2:
+	case Medium::IsoHet: return 1;
+	case Medium::Ortho:
+	case Medium::OrthoHet: return 2;
+	case Medium::Acoustic: return 3;
+	}
+	return 0;
 }
 
-gcmx_path gcmx_effective_path(gcmx_ctx* c) { return c ? effective_path(c) : GCMX_PATH_GENERIC; }
+gcmx_path gcmx_effective_path(gcmx_ctx* c) { return c ? plan_effective_path(facts_of(c)) : GCMX_PATH_GENERIC; }
 gcmx_path gcmx_last_step_path(gcmx_ctx* c) { return c ? c->last_path : GCMX_PATH_AUTO; }
 
 static gcmx_status check_face_nodes(gcmx_ctx* c, int axis, int side, int n_nodes, const int* nodes) {
