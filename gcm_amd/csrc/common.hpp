@@ -61,29 +61,15 @@ struct AxisTable {
 
 // v_max_f64 / v_min_f64 without the operand canonicalisation the compiler adds
 // in front of fmax/fmin for values it cannot prove canonical (loads, LDS).
-#ifndef GCMX_ASM_MINMAX
-#define GCMX_ASM_MINMAX 1
-#endif
-#ifndef GCMX_CLAMP_MINMAX
-#define GCMX_CLAMP_MINMAX 1
-#endif
 __device__ __forceinline__ double vmax(double a, double b) {
-#if GCMX_ASM_MINMAX
 	double r;
 	asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
 	return r;
-#else
-	return fmax(a, b);
-#endif
 }
 __device__ __forceinline__ double vmin(double a, double b) {
-#if GCMX_ASM_MINMAX
 	double r;
 	asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
 	return r;
-#else
-	return fmin(a, b);
-#endif
 }
 
 // The reference's limiter, `if (ans > max) ans = max; else if (ans < min) ans =
@@ -93,20 +79,11 @@ __device__ __forceinline__ double vmin(double a, double b) {
 //   lo = min(x, a), hi = max(x, a):  b >= hi -> hi;  b <= lo -> lo;  else b.
 // Each result is one of the three inputs, so it is the clamp's value (only the
 // sign of an exact zero may differ, as for the clamp form).
-#ifndef GCMX_MED3
-#define GCMX_MED3 1
-#endif
 __device__ __forceinline__ double vmed3(double x, double a, double b) {
 	return vmax(vmin(x, a), vmin(vmax(x, a), b));
 }
 // limit(ans) for the segment (a, b)
-__device__ __forceinline__ double vlimit(double ans, double a, double b) {
-#if GCMX_MED3
-	return vmed3(ans, a, b);
-#else
-	return vmin(vmax(ans, vmin(a, b)), vmax(a, b));
-#endif
-}
+__device__ __forceinline__ double vlimit(double ans, double a, double b) { return vmed3(ans, a, b); }
 
 // EqualDistanceLineInterpolator::minMaxInterpolate for ONE component
 // (EqualDistanceLineInterpolator.hpp:18-43 + 56-71).  s[0..BS] are the values
@@ -137,12 +114,7 @@ __device__ __forceinline__ double newton_minmax(const double (&s)[BS + 1], int k
 	// if (ans > max) ans = max; else if (ans < min) ans = min;
 	// == median(ans, lo, hi) for every non-NaN ans; only the sign of an exact zero
 	// may differ.
-#if GCMX_CLAMP_MINMAX
 	return vlimit(ans, lo, hi);
-#else
-	const double mx = vmax(lo, hi), mn = vmin(lo, hi);
-	return (ans > mx) ? mx : ((ans < mn) ? mn : ans);
-#endif
 }
 
 // Same with compile-time coefficients held in registers by the caller.

@@ -134,19 +134,16 @@ __host__ __device__ constexpr int pair_sig(int S, int P) {
 	return P == 0 ? sig3(S, S) : P == 1 ? sig3(tang1(S), S) : sig3(tang2(S), S);
 }
 
-// GCMX_LAGRANGE (the one-pass step's FMA build, kernels_xyz.hip compiled with
-// GCMX_FMA=1): with floor(q) = 0 and bs <= 2 a foot's interpolant is evaluated
+// GCMX_FMA (the one-pass step's FMA build, kernels_xyz.hip compiled with
+// -DGCMX_FMA=1): with floor(q) = 0 and bs <= 2 a foot's interpolant is evaluated
 // in Lagrange form, w0 s0 + w1 s1 + w2 s2 with the host's weights
 // (lagrange_weights), as one multiply and bs fused multiply-adds: the same
 // polynomial as minMaxInterpolate's Newton form (EqualDistanceLineInterpolator.hpp:56-71)
 // with other roundings, ~1e-16 relative, inside the north star's 1e-10 of the
-// reference (DESIGN.md §3.3); the min-max limiter is unchanged.  The exact build
+// reference (DESIGN.md §3.5); the min-max limiter is unchanged.  The exact build
 // keeps the reference's Newton operations.
 #ifndef GCMX_FMA
 #define GCMX_FMA 0
-#endif
-#ifndef GCMX_LAGRANGE
-#define GCMX_LAGRANGE GCMX_FMA
 #endif
 template <int BS>
 __device__ __forceinline__ double lagrange_minmax(const double (&s)[BS + 1], const double* __restrict__ w) {
@@ -168,7 +165,7 @@ __device__ __forceinline__ void pair_update(const IsoAxis& A, WF W, double& ra, 
 		double sv[BS + 1];
 #pragma unroll
 		for (int i = 0; i <= BS; i++) sv[i] = W(j, sh * i);
-		if constexpr (GCMX_LAGRANGE && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
+		if constexpr (GCMX_FMA && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
 		else return newton_minmax<BS, KF0>(sv, kf, coef);
 	};
 	ra = RowSum<S, false, 2 * P>::go(A, [&](int j) { return interp(j, -1); }, 0.0, true);
@@ -217,21 +214,14 @@ __device__ __forceinline__ void node_update(const IsoAxis& A, WF W, CF C, double
 // 64-bit address arithmetic per component).
 typedef const __attribute__((address_space(1))) double* gcptr;
 typedef __attribute__((address_space(1))) double* gptr;
-#ifndef GCMX_SGPR_BASES
-#define GCMX_SGPR_BASES 1
-#endif
 __device__ __forceinline__ gcptr sgpr_ptr(const double* p) {
 	gcptr q = (gcptr)p;
-#if GCMX_SGPR_BASES
 	asm volatile("" : "+s"(q));
-#endif
 	return q;
 }
 __device__ __forceinline__ gptr sgpr_ptr(double* p) {
 	gptr q = (gptr)p;
-#if GCMX_SGPR_BASES
 	asm volatile("" : "+s"(q));
-#endif
 	return q;
 }
 struct Planes {
@@ -280,10 +270,6 @@ __device__ __forceinline__ double ld_nt_b(const Planes& p, int j, unsigned boff)
 	typedef const __attribute__((address_space(1))) char* gcb;
 	return __builtin_nontemporal_load(reinterpret_cast<gcptr>(reinterpret_cast<gcb>(p.b[j]) + (unsigned long long)boff));
 }
-__device__ __forceinline__ void st_b(const PlanesW& p, int j, unsigned boff, double v) {
-	typedef __attribute__((address_space(1))) char* gb;
-	*reinterpret_cast<gptr>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff) = v;
-}
 __device__ __forceinline__ void st_nt_b(const PlanesW& p, int j, unsigned boff, double v) {
 	typedef __attribute__((address_space(1))) char* gb;
 	__builtin_nontemporal_store(v, reinterpret_cast<gptr>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff));
@@ -301,11 +287,6 @@ __device__ __forceinline__ dpair ld2_nt_b(const Planes& p, int j, unsigned boff)
 	typedef const __attribute__((address_space(1))) char* gcb;
 	typedef const __attribute__((address_space(1))) dpair* gcp2;
 	return __builtin_nontemporal_load(reinterpret_cast<gcp2>(reinterpret_cast<gcb>(p.b[j]) + (unsigned long long)boff));
-}
-__device__ __forceinline__ void st2_b(const PlanesW& p, int j, unsigned boff, dpair v) {
-	typedef __attribute__((address_space(1))) char* gb;
-	typedef __attribute__((address_space(1))) dpair* gp2;
-	*reinterpret_cast<gp2>(reinterpret_cast<gb>(p.b[j]) + (unsigned long long)boff) = v;
 }
 __device__ __forceinline__ void st2_nt_b(const PlanesW& p, int j, unsigned boff, dpair v) {
 	typedef __attribute__((address_space(1))) char* gb;

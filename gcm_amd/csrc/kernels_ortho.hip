@@ -14,7 +14,7 @@ namespace gcmx {
 // (ortho_exact, -ffp-contract=off: the reference's separate multiply and add
 // roundings, bitwise equal to the oracle) and the FMA build (ortho_fma,
 // -DGCMX_FMA=1 -ffp-contract=fast; Lagrange form of the interpolant when
-// floor(q) = 0 and bs <= 2, DESIGN.md §3.3).  gcmx_set_fp_mode selects one.
+// floor(q) = 0 and bs <= 2, DESIGN.md §3.5).  gcmx_set_fp_mode selects one.
 #ifndef GCMX_FMA
 #define GCMX_FMA 0
 #endif

@@ -13,7 +13,7 @@ namespace gcmx {
 // -ffp-contract=off: the reference's separate multiply and add roundings,
 // bitwise equal to the oracle) and as the FMA build (xyz_fma, -DGCMX_FMA=1
 // -ffp-contract=fast: multiply-adds contracted, within the north-star fp64
-// tolerance of the reference; DESIGN.md §3.3).  gcmx_set_fp_mode selects one.
+// tolerance of the reference; DESIGN.md §3.5).  gcmx_set_fp_mode selects one.
 #ifndef GCMX_FMA
 #define GCMX_FMA 0
 #endif
@@ -49,29 +49,19 @@ namespace GCMX_XYZ_NS {
 // gfx950); the output is written with non-temporal stores.
 // Precondition: every y/z ghost of both layers is zero, so the intermediate
 // results at ghost rows / columns are the constant 0.0.
-#ifndef GCMX_XYZ_MINWAVES  // tuning builds only (scripts/ab_build.sh)
-#define GCMX_XYZ_MINWAVES 4
-#endif
-#ifndef GCMX_XYZ_CHUNK
-#define GCMX_XYZ_CHUNK 128
-#endif
-#ifndef GCMX_XYZ_UNROLL
-#define GCMX_XYZ_UNROLL 1
-#endif
-#ifndef GCMX_XYZ_MINWAVES_BS3  // borderSize 3 (tuning builds only: 4 was the round-5 value)
-#define GCMX_XYZ_MINWAVES_BS3 2
-#endif
-#ifndef GCMX_XYZ_TX2  // 1: k_step_tx2 (two x planes per thread) for borderSize <= 2, Z <= 512
-#define GCMX_XYZ_TX2 1
-#endif
+// k_step_tx2 (below) takes every launch with borderSize <= 2 and Z <= 512; this
+// kernel runs borderSize 3 and the rows of 513 .. 1024 the z split does not take.
+constexpr int kXyzMinWaves = 4;  // waves per SIMD (128 VGPRs)
+// borderSize 3 runs at 2 waves per SIMD (4 was the round-5 value): at 4 its
+// windows spill 97 VGPRs to scratch (profiles/r6/bs3_resource_usage.txt).
+constexpr int kXyzMinWavesBs3 = 2;
+constexpr int kXyzChunk = 128;  // rows per block (xyz_chunk_for)
 
-// borderSize 3 runs at 2 waves per SIMD: at 4 (128 VGPRs) its windows spill 97
-// VGPRs to scratch (profiles/r6/bs3_resource_usage.txt).
 // UNI: the launch has Z == ZT (no idle lanes) and the three axes' tables are
 // identical (isotropic medium, equal h): one IsoAxis in scalar registers for all
 // three stages and no idle-lane selects.
 template <int BS, int ZT, bool KF0, bool UNI>
-__global__ __launch_bounds__(ZT, BS >= 3 ? GCMX_XYZ_MINWAVES_BS3 : GCMX_XYZ_MINWAVES) void k_fused_xyz(
+__global__ __launch_bounds__(ZT, BS >= 3 ? kXyzMinWavesBs3 : kXyzMinWaves) void k_fused_xyz(
     const double* __restrict__ in, double* __restrict__ outl, Geo g, IsoAxis AX, IsoAxis AY_,
     IsoAxis AZ_, int x0, int chunk, int nplanes) {
 	const IsoAxis& AY = UNI ? AX : AY_;
@@ -210,7 +200,7 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? GCMX_XYZ_MINWAVES_BS3 : GCMX_XYZ_MINW
 	const unsigned zo = live ? (unsigned)z : (unsigned)Z;
 
 	int buf = 0;
-#pragma unroll GCMX_XYZ_UNROLL
+#pragma unroll 1
 	for (int y = yb; y < ye; y++) {
 		double yv[9];
 		node_update<1, BS, KF0>(
@@ -256,60 +246,11 @@ __global__ __launch_bounds__(ZT, BS >= 3 ? GCMX_XYZ_MINWAVES_BS3 : GCMX_XYZ_MINW
 
 // ------------------------------------------------ two planes per thread --
 
-#ifndef GCMX_TX2_MINWAVES
-#define GCMX_TX2_MINWAVES 2
-#endif
-#ifndef GCMX_TX2_ZS2  // split the ahead-loads around the two nodes' Z stage + stores (-1: unless NB)
-#define GCMX_TX2_ZS2 -1
-#endif
-#ifndef GCMX_TX2_NB  // UNI launches: Z exchange without block barriers (per-wave regions + edge ring)
-#define GCMX_TX2_NB 1
-#endif
-#ifndef GCMX_TX2_SLEEP  // NB: s_sleep argument while a neighbour wave's edges are not there yet
-#define GCMX_TX2_SLEEP 1
-#endif
-#ifndef GCMX_TX2_BUF  // buffer loads/stores: block-uniform offsets in SGPRs (no VALU address math)
-#define GCMX_TX2_BUF 1
-#endif
-#ifndef GCMX_TX2_PROBE_NOX
-#define GCMX_TX2_PROBE_NOX 0
-#endif
-#ifndef GCMX_TX2_DIAG  // tuning builds only: per-wave phase cycle counters (s_memtime)
-#define GCMX_TX2_DIAG 0
-#endif
-#if GCMX_TX2_DIAG
-__device__ unsigned long long g_tx2_diag[16][8];  // [wave in block][phase]: cycles summed over blocks
-#define TX2_T(i)                                                      \
-	do {                                                              \
-		const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-		dt_[i] += now_ - tprev_;                                      \
-		tprev_ = now_;                                                \
-	} while (0)
-#else
-#define TX2_T(i) \
-	do {         \
-	} while (0)
-#endif
-#ifndef GCMX_TX2_GEN2_DEFAULT  // old blocks' share of two generations' rows, percent (0: off; tx2_gen2)
-#define GCMX_TX2_GEN2_DEFAULT 64  // 256^3: 0.530-0.540 against 0.547-0.559 ms off, profiles/r6/s
-#endif
-#ifndef GCMX_TX2_PRIO  // tuning builds only: wave priority while a row's loads are issued (s_setprio)
-#define GCMX_TX2_PRIO 0
-#endif
-#if GCMX_TX2_PRIO
-#define TX2_PRIO_HI() __builtin_amdgcn_s_setprio(GCMX_TX2_PRIO)
-#define TX2_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define TX2_PRIO_HI() \
-	do {              \
-	} while (0)
-#define TX2_PRIO_LO() \
-	do {              \
-	} while (0)
-#endif
-#ifndef GCMX_TX2_ZPERM  // SIMD partners hold neighbouring z blocks (512^3: 3.548-3.570 against 3.572-3.589 ms, profiles/r6/w)
-#define GCMX_TX2_ZPERM 1
-#endif
+constexpr int kTx2MinWaves = 2;  // waves per SIMD (<= 256 VGPRs): one 512-lane block per CU
+// Old blocks' share of two generations' rows, percent (tx2_gen2; the runtime
+// variable GCMX_TX2_GEN2 overrides it, 0: off).  256^3: 0.530-0.540 against
+// 0.547-0.559 ms off, profiles/r6/s
+constexpr int kTx2Gen2Default = 64;
 #ifndef GCMX_TX2_BLKT  // tuning builds only: per-wave start / end times (s_memrealtime, 100 MHz) and the
 #define GCMX_TX2_BLKT 0  // CU of every block of the last k_step_tx2 launch (gcmx_diag_blk*)
 #endif
@@ -317,42 +258,6 @@ __device__ unsigned long long g_tx2_diag[16][8];  // [wave in block][phase]: cyc
 constexpr int kBlkMax = 8192;
 __device__ unsigned long long g_tx2_blk[kBlkMax][8][2];  // [block][wave][start, end]
 __device__ unsigned g_tx2_hw[kBlkMax];                   // HW_ID of the block's wave 0
-#endif
-
-// Timing knobs (A/B builds only; the defaults are the product): per-node face
-// maps compiled into the FACES ghosts; face values read from LDS instead of the
-// kernel arguments; HET_AB 1 = every material uses the kernel-argument table,
-// 2 = also no material-id loads (both give wrong HET results: timing only).
-#ifndef GCMX_TX2_FACEMAP
-#define GCMX_TX2_FACEMAP 1
-#endif
-#ifndef GCMX_TX2_FACE_LDS
-#define GCMX_TX2_FACE_LDS 0
-#endif
-#ifndef GCMX_TX2_STNT
-#define GCMX_TX2_STNT 1  // non-temporal stores of the new layer
-#endif
-#ifndef GCMX_TX2_ALT
-#define GCMX_TX2_ALT 1  // odd y chunks march down (shared halo rows read at the same time)
-#endif
-#ifndef GCMX_TX2_NTOUTER
-#define GCMX_TX2_NTOUTER 0  // timing knob: the outermost window planes by non-temporal loads
-#endif
-#ifndef GCMX_TX2_NTLOAD
-#define GCMX_TX2_NTLOAD 1  // node-only components by non-temporal loads (+0.4 %, profiles/r4/ab)
-#endif
-#ifndef GCMX_HET_AB
-#define GCMX_HET_AB 0
-#endif
-#ifndef GCMX_ZS_PAIRS_FIRST  // z split: block order pairs fastest (1) or the parts of a pair adjacent (0)
-#define GCMX_ZS_PAIRS_FIRST 1  // an XCD's concurrent blocks then cover twice the consecutive pairs: 1024^3 -1.2 % (profiles/r6/n)
-#endif
-
-#ifndef GCMX_TX2_WIDE  // 16-byte global accesses on z-paired half-waves (0: every launch keeps the 8-byte path)
-#define GCMX_TX2_WIDE 1
-#endif
-#ifndef GCMX_TX2_UNROLL  // timing knob: row-loop unroll (5 = the window period: no window moves)
-#define GCMX_TX2_UNROLL 1
 #endif
 
 
@@ -403,11 +308,20 @@ __host__ __device__ constexpr int wcomp(unsigned mask, int q) {
 //
 // Schedule (each choice measured A/B on MI355X): registers hold
 // the two Y windows; the node-only Y components of rows y..y+BS (read back by
-// the same thread only) live in an LDS ring; the Z exchange is one LDS buffer
-// per node with two barriers per row; the first two load pairs of the next row
-// are issued before the Z stage, each node's 9 stores right after its own Z
-// stage, the last pair and the node-only loads when the X stage starts.  One
-// 512-thread block per CU (2 waves/SIMD, <= 256 VGPRs).
+// the same thread only) live in an LDS ring.  The Y results reach the Z stage in
+// one of two ways.  UNI instances (Z == ZT, whole waves): every wave keeps its
+// 64 columns in a region of its own, only the BS edge values per side cross to
+// the neighbour waves through a two-row edge ring, and a per-wave row counter
+// says which rows are there -- no block barrier, so the waves of a block drift
+// apart and overlap their memory phases.  !UNI instances: one block buffer per
+// node between two barriers per row.  Loads of the next row: the UNI instances
+// issue its first two pairs before the Z stage; the !UNI instances issue the
+// first pair there and the second between the two nodes' Z stages.  Each node's
+// 9 stores follow its own Z stage (16-byte path: both nodes' after the second);
+// the last pair and the node-only loads are issued when the X stage starts.
+// One 512-thread block per CU (2 waves/SIMD, <= 256 VGPRs).  Loads and stores
+// are buffer-style: SGPR plane bases, block-uniform offsets, one 32-bit per-lane
+// byte offset; the new layer is written with non-temporal stores.
 //
 // FACES: uniform cubic border conditions on the y/z faces (FaceBC): the ghost
 // rows of the Y stage and the ghost columns of the Z stage are the mirrored
@@ -442,7 +356,7 @@ __host__ __device__ constexpr int wcomp(unsigned mask, int q) {
 // lanes' extra stores sit in the vmcnt queue the row-ahead loads are waited on
 // with, profiles/r6/h.)
 template <int BS, int ZT, bool KF0, bool UNI, bool FACES, bool HET, bool ZS = false, bool WD = false>
-__global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
+__global__ __launch_bounds__(ZT, kTx2MinWaves) void k_step_tx2(
     const double* __restrict__ in, double* __restrict__ outl, Geo g, IsoAxis AX, IsoAxis AY_,
     IsoAxis AZ_, int x0, int chunk, int nplanes, int xb0, int nplanesb, FaceBC fb,
     const IsoAxis* __restrict__ mtab, const uint8_t* __restrict__ mat) {
@@ -463,28 +377,32 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	constexpr int WX = W + 1;  // planes x-BS .. x+1+BS
 	constexpr int LW = ZT + 2 * BS;
 	static_assert(NCX >= 1 && NCY >= 1, "isotropic structure");
-	// NB: Z == ZT, a multiple of 64.  Each wave keeps its own Y results in a region
-	// of 64 + 2 BS slots; only the BS edge values per side cross to the neighbour
-	// waves, through a two-row ring `eg` and a per-wave row counter `rdy` (no block
-	// barrier: the waves of a block drift apart and overlap their memory phases).
-	constexpr bool NB = UNI && GCMX_TX2_NB;
+	// NB (every UNI instance): Z == ZT, a multiple of 64.  Each wave keeps its own Y
+	// results in a region of 64 + 2 BS slots; only the BS edge values per side cross
+	// to the neighbour waves, through a two-row ring `eg` and a per-wave row counter
+	// `rdy` (no block barrier: the waves of a block drift apart and overlap their
+	// memory phases).  The !UNI instances exchange through `zl` between barriers.
+	constexpr bool NB = UNI;
 	constexpr int NW = ZT / 64;
 	static_assert(!NB || ZT % 64 == 0, "NB needs whole waves");
-	// WIDE (launches whose every plane, row and part starts 16-byte aligned,
-	// tx2_wide_ok): lane l < 32 of a wave owns column 2l of the wave's 64-column
-	// block and lane l + 32 column 2l + 1, so one 16-byte access of lane l covers
-	// the columns of lanes l and l + 32.  A load brings those two columns of ONE
-	// plane -- the lower half-wave addresses plane a, the upper half plane b --
-	// and half_swap turns the two halves' pairs into every lane's own column of
-	// planes a and b; stores run the same exchange backwards.  `z`, `ln`, `wv`
-	// keep their meaning (the lane's column); only the LDS slots are by lane.
-	constexpr bool WIDE = WD && NB && GCMX_TX2_WIDE && GCMX_TX2_BUF;
-	static_assert(!WD || WIDE, "wide instance launched without its path compiled in");
+	// WIDE: the instance's WD argument, which only barrier-free (UNI) instances
+	// may set.  The launcher sets it where every plane, row and part of the launch
+	// starts 16-byte aligned (tx2_wide_ok) and the instance gains from it (go_uni).
+	// Lane l < 32 of a wave owns column 2l of the wave's 64-column block and lane
+	// l + 32 column 2l + 1, so one 16-byte access of lane l covers the columns of
+	// lanes l and l + 32.  A load brings those two columns of ONE plane -- the
+	// lower half-wave addresses plane a, the upper half plane b -- and half_swap
+	// turns the two halves' pairs into every lane's own column of planes a and b;
+	// stores run the same exchange backwards.  `z`, `ln`, `wv` keep their meaning
+	// (the lane's column); only the LDS slots are by lane.
+	constexpr bool WIDE = WD && NB;
+	static_assert(!WD || WIDE, "wide instance needs the barrier-free exchange (UNI)");
 	// WIDE: a wave's region holds its even columns -2 .. 64 in slots 0 .. 33 and
 	// its odd columns -1 .. 65 in slots 34 .. 67 (each half-wave reads and writes
 	// 32 consecutive slots: no bank conflicts, as 64 consecutive ones by z)
 	constexpr int RW = WIDE ? 68 : 64 + 2 * BS;
-	constexpr bool ZS2 = GCMX_TX2_ZS2 < 0 ? !NB : GCMX_TX2_ZS2 != 0;
+	// the barrier instances split the ahead-loads around the two nodes' Z stage + stores
+	constexpr bool ZS2 = !NB;
 	__shared__ double zl[NB ? 1 : 2][NB ? 1 : NWZ][NB ? 1 : LW];  // Y results of both nodes (Z stage input)
 	__shared__ double rg[NB ? NW : 1][NB ? 2 : 1][NB ? NWZ : 1][NB ? RW : 1];
 	__shared__ double eg[NB ? 2 : 1][NB ? NW : 1][2][NB ? 2 : 1][NB ? NWZ : 1][BS];  // [row&1][wave][side][node][comp][k]
@@ -496,26 +414,22 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	// it -- the software pipeline collapses (measured: HET 256^3 +34 %).
 	__shared__ IsoAxis hlds[HET ? kHetMaxMaterials : 1];
 	__shared__ double hode[HET ? kHetMaxMaterials : 1];  // HET: folded ODE factor per material
-	__shared__ double flds[FACES && GCMX_TX2_FACE_LDS ? 4 : 1][9];  // 2 f(t) of the y/z faces
 
-#if GCMX_TX2_ZPERM
 	// z blocks of 64 columns dealt so that the two waves sharing a SIMD (w and
 	// w + 4 of a 512-lane block) hold neighbouring z blocks 2w and 2w + 1
+	// (512^3: 3.548-3.570 against 3.572-3.589 ms in block order, profiles/r6/w)
 	const int z = [] {
 		int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 		if constexpr (ZT == 512) w = w < 4 ? 2 * w : 2 * (w - 4) + 1;
 		const int l = (int)(threadIdx.x & 63);
 		return w * 64 + (WIDE ? ((l & 31) << 1) | (l >> 5) : l);
 	}();
-#else
-	const int z = WIDE ? (int)((threadIdx.x & ~63u) | ((threadIdx.x & 31u) << 1) | ((threadIdx.x >> 5) & 1u)) : (int)threadIdx.x;
-#endif
 #if GCMX_TX2_BLKT
 	const unsigned long long blk_t0_ = __builtin_amdgcn_s_memrealtime();
 #endif
 	const int Y = g.sizes[1], Z = g.sizes[2];
 	int x, yb, ye, xbeg, xend;
-	bool rev;  // this block marches its rows downwards (odd chunks, GCMX_TX2_ALT)
+	bool rev;  // this block marches its rows downwards (odd chunks, see `run`)
 	int zp = 0;                                    // ZS: this block's part of the z row
 	const int nz = ZS ? g.sizes[2] / ZT : 1;
 	{  // XCD-aware chunk-major block order (see k_fused_xyz) over the plane pairs of
@@ -529,11 +443,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		const int npa = (nplanes + pa + 1) / 2;
 		const int npair = npa + (nplanesb > 0 ? (nplanesb + pb + 1) / 2 : 0);
 		const int T = (int)gridDim.x, b = (int)blockIdx.x;
-		int p = xcd_order(b, T);
-		if constexpr (ZS && !GCMX_ZS_PAIRS_FIRST) {  // the parts of one (pair, chunk) are neighbours in the order
-			zp = p % nz;
-			p /= nz;
-		}
+		const int p = xcd_order(b, T);
 		int q = p % npair;
 		int cidx = p / npair;  // chunk index
 		if (!ZS && chunk < 0) {
@@ -557,7 +467,10 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		x = q < npa ? x0 - pa + 2 * q : xb0 - pb + 2 * (q - npa);
 		xbeg = q < npa ? x0 : xb0;
 		xend = q < npa ? x0 + nplanes : xb0 + nplanesb;
-		if constexpr (ZS && GCMX_ZS_PAIRS_FIRST) {  // pairs fastest, then parts, then chunks
+		// ZS: pairs fastest, then parts, then chunks.  An XCD's concurrent blocks then
+		// cover twice the consecutive pairs of an order with the parts of a pair
+		// adjacent: 1024^3 -1.2 % (profiles/r6/n)
+		if constexpr (ZS) {
 			zp = cidx % nz;
 			cidx /= nz;
 		}
@@ -565,7 +478,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 			yb = cidx * chunk;
 			ye = min(yb + chunk, Y);
 		}
-		rev = GCMX_TX2_ALT && (cidx & 1);
+		rev = cidx & 1;
 	}
 	const bool one = x >= xbeg;  // node x is ours (else only x + 1 is)
 	const bool two = x + 1 < xend;
@@ -581,7 +494,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	// Memory accessors.  ldx(j, k, r): component j of plane x - BS + k (the last
 	// plane clamped when x + 1 is not ours), row r, this lane's column;
 	// stz(c, t, y, v): component c of node (x + t, y) of the output layer.
-#if GCMX_TX2_BUF
+	// Buffer-style: block-uniform offsets in SGPRs, no VALU address math.
 	const Planes src(in + pbase, g.cs);
 	const PlanesW out_p(outl + pbase, g.cs);
 	const unsigned zpart = ZS ? (unsigned)(zp * ZT) : 0u;      // ZS: first column of this part
@@ -589,26 +502,19 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	const unsigned lv = (zpart + (unsigned)zc) * 8u, sv = (zpart + zo) * 8u;  // per-lane byte offsets
 	const unsigned pxm = plane - (unsigned)BS * stx;      // plane x - BS, row 0, column 0
 	auto ldx = [&](int j, int k, int r) {
-#if GCMX_TX2_PROBE_NOX  // timing probe only (wrong results): x-neighbour loads re-read the own planes
-		k = k < BS ? BS : (k > BS + 1 ? BS + 1 : k);
-#endif
 		// planes outside the valid range (x - BS when x is not ours, x + 1 + BS when
 		// x + 1 is not ours) are read by the discarded node only: clamp them
 		const int d = (k == WX - 1 && !two) ? 2 * BS : (k == 0 && !one) ? 1 : k;
-		if (GCMX_TX2_NTOUTER && (k == 0 || k == WX - 1))
-			return ld_nt_b(src, j, opaque_u32(lv + (pxm + (unsigned)d * stx + (unsigned)r * sty) * 8u));
 		return ld_b(src, j, opaque_u32(lv + (pxm + (unsigned)d * stx + (unsigned)r * sty) * 8u));
 	};
-	// the node-only components of the own planes: read once, by this lane only
+	// the node-only components of the own planes: read once, by this lane only,
+	// so by non-temporal loads (+0.4 % against plain ones, profiles/r4/ab)
 	auto ldc = [&](int j, int k, int r) {
-		if constexpr (!GCMX_TX2_NTLOAD) return ldx(j, k, r);
 		const int d = (k == WX - 1 && !two) ? 2 * BS : (k == 0 && !one) ? 1 : k;
 		return ld_nt_b(src, j, opaque_u32(lv + (pxm + (unsigned)d * stx + (unsigned)r * sty) * 8u));
 	};
-	auto stz = [&](int c, int t, int y, double v) {
-		const unsigned o = opaque_u32(sv + (plane + (unsigned)t * stx + (unsigned)y * sty) * 8u);
-		if constexpr (GCMX_TX2_STNT) st_nt_b(out_p, c, o, v);
-		else st_b(out_p, c, o, v);
+	auto stz = [&](int c, int t, int y, double v) {  // non-temporal, as every store of the new layer
+		st_nt_b(out_p, c, opaque_u32(sv + (plane + (unsigned)t * stx + (unsigned)y * sty) * 8u), v);
 	};
 	// WIDE accessors.  ldw(j, ka, kb, r): the lane's 16 bytes (columns 2l, 2l + 1 of
 	// its wave's block) of component j, row r, of window plane ka (lower half-wave)
@@ -626,32 +532,16 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	auto stw = [&](int c, int y, double v0, double v1) {
 		const unsigned o = opaque_u32(lw + (plane + (hsel ? stx : 0u) + (unsigned)y * sty) * 8u);
 		const dpair v = {v0, v1};
-		if constexpr (GCMX_TX2_STNT) st2_nt_b(out_p, c, o, v);
-		else st2_b(out_p, c, o, v);
+		st2_nt_b(out_p, c, o, v);
 	};
-#else
-	const unsigned base = plane + zc;
-	const Planes src(in + pbase, g.cs);
-	const PlanesW out_p(outl + pbase, g.cs);
-	auto ldx = [&](int j, int k, int r) {
-		const int d = (k == WX - 1 && !two) ? BS : (k == 0 && !one) ? 1 - BS : k - BS;
-		return src.ld(j, base + (unsigned)r * sty + (unsigned)d * stx);
-	};
-	auto ldc = [&](int j, int k, int r) { return ldx(j, k, r); };
-	auto stz = [&](int c, int t, int y, double v) { out_p.st_nt(c, plane + (unsigned)y * sty + zo + (unsigned)t * stx, v); };
-#endif
 	// per-material table k (the lane's own material), from the LDS copy made at
 	// kernel start.  Measured alternatives: scalar loads through
 	// the constant address space spill VGPRs; separate one-table / two-table X
 	// paths double the X stage's code; both are slower.
-	auto mt = [&](unsigned k) -> const IsoAxis& {
-		if constexpr (GCMX_HET_AB >= 1) return AX;
-		return hlds[k];
-	};
-	auto two_v = [&](int f, int j) -> double {
-		if constexpr (FACES && GCMX_TX2_FACE_LDS) return flds[f][j];
-		return fb.two_v[f][j];
-	};
+	auto mt = [&](unsigned k) -> const IsoAxis& { return hlds[k]; };
+	// (a lambda on purpose: with ghost_rule reading fb.two_v directly the FACES
+	// instances come out with other SGPR spill counts, i.e. other instructions)
+	auto two_v = [&](int f, int j) -> double { return fb.two_v[f][j]; };
 	// The condition of face f at node x + t (pos = the node's z on y faces, its y
 	// on z faces), resolved once per node: the overridden components and their
 	// 2 f(t) (components in `need` only).  A face with a per-node map (partial
@@ -664,7 +554,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	auto ghost_rule = [&](int f, int t, int pos, unsigned need) -> GhostRule {
 		GhostRule r;
 		r.none = false;
-		if (GCMX_TX2_FACEMAP && fb.map[f]) {
+		if (fb.map[f]) {
 			const int xx = (t == 1 && !two) ? x : (t == 0 && !one) ? x + 1 : x + t;
 			const unsigned c = fb.map[f][(size_t)xx * (f < 2 ? Z : Y) + pos];
 			r.none = c == kNoFaceCond;
@@ -728,7 +618,6 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	auto pair_load = [&](auto PC, PairWin& w, int r) {
 		constexpr int P = decltype(PC)::value;
 		if constexpr (WIDE) {  // raw half-wave pairs: pair_fix before use
-#if GCMX_TX2_BUF
 #pragma unroll
 			for (int m = 0; m < WX / 2; m++) {
 				const dpair a = ldw(pair_vel(0, P), 2 * m, 2 * m + 1, r, false);
@@ -736,7 +625,6 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 				w[0][2 * m] = a.x, w[0][2 * m + 1] = a.y;
 				w[1][2 * m] = b.x, w[1][2 * m + 1] = b.y;
 			}
-#endif
 			return;
 		}
 #pragma unroll
@@ -768,7 +656,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 				pair_update<0, BS, true, P>(
 				    t ? A1 : A0, [&](int j, int o) { return j == pair_vel(0, P) ? w[0][t + BS + o] : w[1][t + BS + o]; },
 				    rr[t][2 * P], rr[t][2 * P + 1]);
-		} else if constexpr (KF0 && !GCMX_LAGRANGE) {
+		} else if constexpr (KF0 && !GCMX_FMA) {
 			const IsoAxis& AS = A0;  // one table for both nodes
 			const double* c = (P == 0) ? AS.c1 : AS.c2;
 			double im[2][2], ip[2][2];  // [vel/sig][node]
@@ -822,14 +710,12 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	};
 	auto cv_load = [&](double (&cv)[2][9], int r) {
 		if constexpr (WIDE) {  // the own planes as one pair (raw: half_swap in x_compute)
-#if GCMX_TX2_BUF
 #pragma unroll
 			for (int j = 0; j < 9; j++)
 				if ((CMX >> j) & 1u) {
-					const dpair v = ldw(j, BS, BS + 1, r, GCMX_TX2_NTLOAD != 0);
+					const dpair v = ldw(j, BS, BS + 1, r, true);
 					cv[0][j] = v.x, cv[1][j] = v.y;
 				}
-#endif
 			return;
 		}
 #pragma unroll
@@ -886,18 +772,13 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		}
 	};
 	// HET: the two nodes' materials of row r as one key (node x in bits 0-7)
-	auto key_of = [&](int r) -> unsigned {
-		if constexpr (GCMX_HET_AB >= 2) return 0u;
-		return mat_of(0, r) | (mat_of(1, r) << 8);
-	};
+	auto key_of = [&](int r) -> unsigned { return mat_of(0, r) | (mat_of(1, r) << 8); };
 	// key: key_of(r), loaded ahead by the caller (HET)
 	auto x_stage = [&](const XPre& pre, int r, double (&xr)[2][9], unsigned key) {
 		PairWin wc;
 		double cv[2][9];
-		TX2_PRIO_HI();
 		pair_load(P2{}, wc, r);
 		cv_load(cv, r);
-		TX2_PRIO_LO();
 		sched_fence();
 		if constexpr (HET) {
 			const unsigned m0 = key & 255u, m1 = key >> 8;
@@ -918,12 +799,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 			reinterpret_cast<unsigned*>(hlds)[i] = reinterpret_cast<const unsigned*>(mtab)[i];
 		if (fb.ode_on && fb.ode_f && z < kHetMaxMaterials) hode[z] = fb.ode_f[z];
 	}
-	if constexpr (FACES && GCMX_TX2_FACE_LDS) {
-#pragma unroll
-		for (int c = 0; c < 36; c++)
-			if (z == c) flds[c / 9][c % 9] = fb.two_v[c / 9][c % 9];
-	}
-	if constexpr (HET || (FACES && GCMX_TX2_FACE_LDS)) __syncthreads();
+	if constexpr (HET) __syncthreads();
 	// The row march, in either direction (REV: from the chunk's last row down).
 	// Odd chunks march down, so the halo rows two adjacent chunks both compute
 	// the X stage of are read by both blocks at the same time -- both at the
@@ -1001,10 +877,6 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		return r < Y + BS - 1 ? r : Y + BS - 1;
 	};
 
-#if GCMX_TX2_DIAG
-	unsigned long long dt_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-	unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
-#endif
 	// Y stage of row y for both nodes (window + node-only ring)
 	auto y_stage = [&](int y, double (&yv)[2][9]) {
 		const double* cp = cl_at(y);
@@ -1103,7 +975,7 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 				const int b =
 				    wv < NW - 1 ? __hip_atomic_load(&rdy[wv + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : it;
 				if (__builtin_amdgcn_readfirstlane(min(a, b)) >= it) break;
-				if constexpr (GCMX_TX2_SLEEP > 0) __builtin_amdgcn_s_sleep(GCMX_TX2_SLEEP);
+				__builtin_amdgcn_s_sleep(1);  // a neighbour wave's edges are not there yet
 			}
 			asm volatile("" ::: "memory");
 			if (ln < BS && wv > 0) {
@@ -1152,14 +1024,12 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 	// WIDE: both nodes' results of row y, 9 16-byte stores: plane x from the lower
 	// half-wave, plane x + 1 from the upper
 	auto z_store_wide = [&](int y, double (&zv)[2][9]) {
-#if GCMX_TX2_BUF
 #pragma unroll
 		for (int c = 0; c < 9; c++) half_swap(zv[0][c], zv[1][c]);
 		if ((hsel ? two : one) && !seam_pair) {
 #pragma unroll
 			for (int c = 0; c < 9; c++) stw(c, y, zv[0][c], zv[1][c]);
 		}
-#endif
 	};
 	// X stage of row y+S*(BS+1) -> window slot W-1 (ghost rows: zero, or a face's mirror)
 	auto x_enter = [&](int y, const XPre& pre, unsigned kn) {
@@ -1195,23 +1065,17 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		unsigned kn = 0;  // HET: row rn's materials, one row ahead of its X stage
 		if constexpr (HET) kn = key_of(rn);
 		y_stage(y, yv);
-		TX2_T(0);
 		publish(it, y, yv);
-		TX2_T(2);
 		if constexpr (ZS2) {
 			sched_fence();
 			pair_load(P0{}, pre.a, rn);
 			sched_fence();
 		} else {  // loads older than this row's stores
 			sched_fence();
-			TX2_PRIO_HI();
 			x_load_ahead(pre, rn);
-			TX2_PRIO_LO();
 			sched_fence();
 		}
-		TX2_T(6);
 		collect(it);
-		TX2_T(4);
 #pragma unroll
 		for (int t = 0; t < 2; t++) {  // each node's stores right after its Z stage
 			if constexpr (ZS2) {
@@ -1224,13 +1088,8 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 			z_stage_store(t, y, yv, zv[t]);
 		}
 		if constexpr (WIDE) z_store_wide(y, zv);
-		TX2_T(3);
 		x_enter(y, pre, kn);
-		TX2_T(5);
 	};
-#if GCMX_TX2_UNROLL > 1
-#pragma unroll GCMX_TX2_UNROLL
-#endif
 	for (int it = 0; it < ye - yb; it++) row(REV ? ye - 1 - it : yb + it, it);
 #if GCMX_TX2_BLKT
 	if ((threadIdx.x & 63) == 0 && blockIdx.x < (unsigned)kBlkMax && threadIdx.x < 512) {
@@ -1238,12 +1097,6 @@ __global__ __launch_bounds__(ZT, GCMX_TX2_MINWAVES) void k_step_tx2(
 		g_tx2_blk[blockIdx.x][threadIdx.x / 64][0] = blk_t0_;
 		g_tx2_blk[blockIdx.x][threadIdx.x / 64][1] = t1;
 		if (threadIdx.x == 0) g_tx2_hw[blockIdx.x] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
-	}
-#endif
-#if GCMX_TX2_DIAG
-	if ((threadIdx.x & 63) == 0) {
-		const int wv = threadIdx.x / 64;
-		for (int i = 0; i < 8; i++) atomicAdd(&g_tx2_diag[wv][i], dt_[i]);
 	}
 #endif
 	};
@@ -1403,9 +1256,8 @@ static const char* tx2_name() {
 	return s.c_str();
 }
 // The barrier-free instances (UNI) take the wide path when the launch allows it.
-constexpr bool kTx2Wide = (GCMX_TX2_WIDE != 0) & (GCMX_TX2_NB != 0) & (GCMX_TX2_BUF != 0);
 static bool tx2_wide_ok(const Geo& g, const double* in, const double* out) {
-	return kTx2Wide && wide_layout_ok(g) && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
+	return wide_layout_ok(g) && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
 }
 template <int BS, int ZT, bool KF0, bool UNI>
 static const char* xyz_name() {
@@ -1440,7 +1292,7 @@ static int device_cus();
 static int tx2_gen2(int Y, int npair, int chunk, int T, int per_cu) {
 	static const int pct = [] {
 		const char* e = std::getenv("GCMX_TX2_GEN2");
-		return e ? std::atoi(e) : GCMX_TX2_GEN2_DEFAULT;
+		return e ? std::atoi(e) : kTx2Gen2Default;
 	}();
 	if (pct <= 50 || pct >= 100 || per_cu != 2 || T != 2 * device_cus() || T % 16 || (T / 2) % npair) return chunk;
 	const int nchunk = T / npair;
@@ -1463,12 +1315,12 @@ static int device_cus() {
 	return n;
 }
 
-// Rows per block (k_fused_xyz): GCMX_XYZ_CHUNK (128) while the launch still has >= 1024 blocks
+// Rows per block (k_fused_xyz): kXyzChunk (128) while the launch still has >= 1024 blocks
 // (two rounds of the 512 resident blocks, 2 per CU); thinner slabs (multi-GPU
 // X slabs, the boundary planes) halve it, down to 16 rows, to keep every CU
 // busy.  Each block recomputes 2*BS X rows in its prologue, so a chunk of c
 // rows costs (c + 2*BS) / c of the X stage.  `req` > 0 forces a value.
-static int xyz_chunk_for(int Y, int nplanes, int req, int start = GCMX_XYZ_CHUNK, int min_blocks = 1024) {
+static int xyz_chunk_for(int Y, int nplanes, int req, int start = kXyzChunk, int min_blocks = 1024) {
 	int chunk = req > 0 ? req : start;
 	if (req <= 0)
 		while (chunk > 16 && (long long)((Y + chunk - 1) / chunk) * nplanes < min_blocks) chunk /= 2;
@@ -1495,7 +1347,7 @@ static void launch_zs(const double* in, double* out, const Geo& g, const IsoAxis
 		                   a[0], a[1], a[2], x0, chunk, x1 - x0, xb0, nb, f, nullptr, nullptr);
 		*kname = tx2_name<BS, P, true, true, FACES, false, true, WD>();
 	};
-	if (tx2_wide_ok(g, in, out)) go(std::integral_constant<bool, kTx2Wide>{});
+	if (tx2_wide_ok(g, in, out)) go(std::true_type{});
 	else go(std::false_type{});
 	// the cut columns: 256 / (4 BS) planes per block, 64-row chunks
 	const int np = (x1 - x0) + nb, pb = 256 / (4 * BS), sch = std::min(64, g.sizes[1]);
@@ -1512,56 +1364,57 @@ static void launch_xyz_t(const double* in, double* out, const Geo& g, const IsoA
 	for (int s = 0; s < 3; s++) kf0 = kf0 && a[s].kf1 == 0 && a[s].kf2 == 0;
 	const bool uni = kf0 && g.sizes[2] == ZT && same_axis(a[0], a[1]) && same_axis(a[0], a[2]);
 	if constexpr (BS <= 2 && ZT <= 512) {
-		if (GCMX_XYZ_TX2 || fb) {
-			const int nb = xb1 > xb0 ? xb1 - xb0 : 0;
-			// global pairs (k_step_tx2): a range starting at an odd global plane
-			// begins with a half pair
-			const int npair = (x1 - x0 + ((g.gx0 + x0) & 1) + 1) / 2 +
-			                  (nb > 0 ? (nb + ((g.gx0 + xb0) & 1) + 1) / 2 : 0);
-			// resident blocks: 2 waves per SIMD (<= 256 VGPRs), i.e. 512 / ZT per CU
-			const int chunk = tx2_chunk_for(g.sizes[1], npair, req_chunk, device_cus() * (512 / ZT));
-			const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * npair);
-			const int cparam = req_chunk > 0 ? chunk : tx2_gen2(g.sizes[1], npair, chunk, (int)grid.x, 512 / ZT);
-			const FaceBC none{};
-			const FaceBC& f = fb ? *fb : none;
-			const IsoAxis* mt = het ? het->tab : nullptr;
-			const uint8_t* mi = het ? het->ids : nullptr;
-			auto go = [&](auto K, const char* name) {
-				hipLaunchKernelGGL(K, grid, dim3(ZT), 0, st, in, out, g, a[0], a[1], a[2], x0, cparam, x1 - x0, xb0,
-				                   nb, f, mt, mi);
-				*kname = name;
-			};
-			// the UNI instances: 16-byte accesses where the layout allows, else the 8-byte path
-			const bool wide = tx2_wide_ok(g, in, out);
-			auto go_uni = [&](auto FC, auto HC) {
-				constexpr bool F = decltype(FC)::value, H = decltype(HC)::value;
-				// per-node materials at borderSize 2 keep the 8-byte path: holding node
-				// 0's results across node 1's Z stage spills there (24-80 B of scratch)
-				// and so do the 256-lane instances: with two blocks per CU the wide path
-				// measured slower (256^3: 4 of 5 alternating pairs, +0.5 .. +4.6 %,
-				// profiles/wide/bench_256_*.jsonl), against -2.3 % at one 512-lane block
-				constexpr bool W = kTx2Wide && !(H && BS == 2) && ZT != 256;
-				if (wide && W) go(k_step_tx2<BS, ZT, true, true, F, H, false, W>,
-				                  tx2_name<BS, ZT, true, true, F, H, false, W>());
-				else go(k_step_tx2<BS, ZT, true, true, F, H>, tx2_name<BS, ZT, true, true, F, H>());
-			};
-			if (het) {  // the caller checked Z == ZT, KF0 and equal axes per material
-				if (fb && fb->on) go_uni(std::true_type{}, std::true_type{});
-				else go_uni(std::false_type{}, std::true_type{});
-				return;
-			}
-			if (fb && fb->on) {
-				if (uni) go_uni(std::true_type{}, std::false_type{});
-				else if (kf0) go(k_step_tx2<BS, ZT, true, false, true, false>, tx2_name<BS, ZT, true, false, true, false>());
-				else go(k_step_tx2<BS, ZT, false, false, true, false>, tx2_name<BS, ZT, false, false, true, false>());
-			} else {
-				if (uni) go_uni(std::false_type{}, std::false_type{});
-				else if (kf0) go(k_step_tx2<BS, ZT, true, false, false, false>, tx2_name<BS, ZT, true, false, false, false>());
-				else go(k_step_tx2<BS, ZT, false, false, false, false>, tx2_name<BS, ZT, false, false, false, false>());
-			}
+		const int nb = xb1 > xb0 ? xb1 - xb0 : 0;
+		// global pairs (k_step_tx2): a range starting at an odd global plane
+		// begins with a half pair
+		const int npair = (x1 - x0 + ((g.gx0 + x0) & 1) + 1) / 2 +
+		                  (nb > 0 ? (nb + ((g.gx0 + xb0) & 1) + 1) / 2 : 0);
+		// resident blocks: 2 waves per SIMD (<= 256 VGPRs), i.e. 512 / ZT per CU
+		const int chunk = tx2_chunk_for(g.sizes[1], npair, req_chunk, device_cus() * (512 / ZT));
+		const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * npair);
+		const int cparam = req_chunk > 0 ? chunk : tx2_gen2(g.sizes[1], npair, chunk, (int)grid.x, 512 / ZT);
+		const FaceBC none{};
+		const FaceBC& f = fb ? *fb : none;
+		const IsoAxis* mt = het ? het->tab : nullptr;
+		const uint8_t* mi = het ? het->ids : nullptr;
+		auto go = [&](auto K, const char* name) {
+			hipLaunchKernelGGL(K, grid, dim3(ZT), 0, st, in, out, g, a[0], a[1], a[2], x0, cparam, x1 - x0, xb0,
+			                   nb, f, mt, mi);
+			*kname = name;
+		};
+		// the UNI instances: 16-byte accesses where the layout allows, else the 8-byte path
+		const bool wide = tx2_wide_ok(g, in, out);
+		auto go_uni = [&](auto FC, auto HC) {
+			constexpr bool F = decltype(FC)::value, H = decltype(HC)::value;
+			// per-node materials at borderSize 2 keep the 8-byte path: holding node
+			// 0's results across node 1's Z stage spills there (24-80 B of scratch)
+			// and so do the 256-lane instances: with two blocks per CU the wide path
+			// measured slower (256^3: 4 of 5 alternating pairs, +0.5 .. +4.6 %,
+			// profiles/wide/bench_256_*.jsonl), against -2.3 % at one 512-lane block
+			constexpr bool W = !(H && BS == 2) && ZT != 256;
+			if (wide && W) go(k_step_tx2<BS, ZT, true, true, F, H, false, W>,
+			                  tx2_name<BS, ZT, true, true, F, H, false, W>());
+			else go(k_step_tx2<BS, ZT, true, true, F, H>, tx2_name<BS, ZT, true, true, F, H>());
+		};
+		if (het) {  // the caller checked Z == ZT, KF0 and equal axes per material
+			if (fb && fb->on) go_uni(std::true_type{}, std::true_type{});
+			else go_uni(std::false_type{}, std::true_type{});
 			return;
 		}
+		if (fb && fb->on) {
+			if (uni) go_uni(std::true_type{}, std::false_type{});
+			else if (kf0) go(k_step_tx2<BS, ZT, true, false, true, false>, tx2_name<BS, ZT, true, false, true, false>());
+			else go(k_step_tx2<BS, ZT, false, false, true, false>, tx2_name<BS, ZT, false, false, true, false>());
+		} else {
+			if (uni) go_uni(std::false_type{}, std::false_type{});
+			else if (kf0) go(k_step_tx2<BS, ZT, true, false, false, false>, tx2_name<BS, ZT, true, false, false, false>());
+			else go(k_step_tx2<BS, ZT, false, false, false, false>, tx2_name<BS, ZT, false, false, false, false>());
+		}
+		return;
 	}
+	// borderSize 3, or a row longer than 512.  (The rest of this function is not
+	// reached at borderSize <= 2, ZT <= 512, but stays outside an `else`: that
+	// would drop those k_fused_xyz instances from the code object.)
 	if (xb1 > xb0) {  // k_fused_xyz has no second range: two launches
 		launch_xyz_t<BS, ZT>(in, out, g, a, x0, x1, 0, 0, st, req_chunk, fb, kname, het);
 		x0 = xb0;
@@ -1609,14 +1462,6 @@ extern "C" int gcmx_diag_blk(unsigned long long* t, unsigned* hw) {
 	if (hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_tx2_hw), sizeof(g_tx2_hw)) != hipSuccess) return -1;
 	static unsigned long long zero[kBlkMax][8][2];
 	return hipMemcpyToSymbol(HIP_SYMBOL(g_tx2_blk), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif
-
-#if GCMX_TX2_DIAG && !GCMX_FMA
-extern "C" int gcmx_diag_tx2(unsigned long long* out) {  // 16 x 8 counters, then reset
-	if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tx2_diag), sizeof(g_tx2_diag)) != hipSuccess) return -1;
-	static const unsigned long long zero[16][8] = {};
-	return hipMemcpyToSymbol(HIP_SYMBOL(g_tx2_diag), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 #endif
 

@@ -178,7 +178,7 @@ bool zs_admissible(const Geo& g, const IsoAxis* a);
 int step_free_cus(const Geo& g, int x0, int x1, int req_chunk, int cus = -1);  // cus <= 0: the device's
 // Two builds of the one-pass step kernels (kernels_xyz.hip): xyz_exact keeps the
 // reference's roundings (bitwise), xyz_fma contracts multiply-adds
-// (gcmx_set_fp_mode; DESIGN.md §3.3).
+// (gcmx_set_fp_mode; DESIGN.md §3.5).
 namespace xyz_exact {
 bool launch_fused_xyz(const double* in, double* out, const Geo& g, const IsoAxis* a, int x0,
                       int x1, hipStream_t st, int chunk = 0, const FaceBC* faces = nullptr,

@@ -178,7 +178,7 @@ __device__ __forceinline__ void opair_update(const OrthoAxis& A, WF W, double& r
 		double sv[BS + 1];
 #pragma unroll
 		for (int i = 0; i <= BS; i++) sv[i] = W(j, sh * i);
-		if constexpr (GCMX_LAGRANGE && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
+		if constexpr (GCMX_FMA && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
 		else return newton_minmax<BS, KF0>(sv, kf, coef);
 	};
 	ra = ORowSum<S, false, 2 * P>::go(A, [&](int j) { return interp(j, 1); }, 0.0, true);
