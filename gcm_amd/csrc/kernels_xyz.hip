@@ -596,6 +596,31 @@ __global__ __launch_bounds__(ZT, kTx2MinWaves) void k_step_tx2(
 		return ZS && sc(cb) && sc(cb + 1);
 	}();
 	const int ci = WIDE ? (int)threadIdx.x : z;  // the lane's slot in the `cl` ring (read back by itself only)
+	// NB: the hand-over lanes of `collect`.  A side of a wave's ring row is NE
+	// contiguous values [node t][component q][k]; HARDWARE lane e < NE of the lower
+	// half-wave takes value e of the left neighbour's right side, lane 32 + e value
+	// e of the right neighbour's left side, each into the own halo slot of column
+	// k - BS (left) or 64 + k (right).  Wave 0 has no left and wave NW - 1 no right
+	// neighbour: those halo slots keep their zeros or publish's face ghosts, and no
+	// lane of that half copies.  Both places are fixed for the launch and share one
+	// register (the row loop has none to spare): `hpk` = the element of ring row 0
+	// in `eg` (collect adds the row) in the low half, the element of `rg` in the
+	// high half; sign bit set: the lane does not copy.
+	constexpr int NE = 2 * NWZ * BS;  // edge values per side
+	constexpr int ESZ = NW * 2 * NE;  // doubles per ring row
+	static_assert(!NB || NE <= 32, "one edge value per lane of a half-wave");
+	static_assert(!NB || (2 * ESZ <= 0x10000 && NW * 2 * NWZ * RW <= 0x8000), "hpk: 16 + 15 bits");
+	unsigned hpk = ~0u;
+	if constexpr (NB && NW > 1) {
+		const int e = (int)(threadIdx.x & 31u);
+		const bool right = (threadIdx.x & 32u) != 0;
+		if (e < NE && (right ? wv < NW - 1 : wv > 0)) {
+			const int k = e % BS, q = (e / BS) % NWZ, t = e / (BS * NWZ);
+			const int src = ((right ? wv + 1 : wv - 1) * 2 + (right ? 0 : 1)) * NE + e;
+			const int dst = ((wv * 2 + t) * NWZ + q) * RW + rs(right ? 64 + k : k - BS);
+			hpk = (unsigned)src | ((unsigned)dst << 16);
+		}
+	}
 	if constexpr (NB) {  // zero halos (z ghosts stay zero without a z face); counters
 		if (ln < BS || ln >= 64 - BS) {
 			const int hs = rs(ln < BS ? ln - BS : ln + BS);
@@ -926,23 +951,30 @@ __global__ __launch_bounds__(ZT, kTx2MinWaves) void k_step_tx2(
 			double* egp = ln < BS ? &eg[es][wv][0][0][0][ln] : &eg[es][wv][1][0][0][ln - (64 - BS)];
 			const bool edge = ln < BS || ln >= 64 - BS;
 			asm volatile("" ::: "memory");  // after the previous row's Z-stage reads of rg
+			// The edges first: the neighbour waves wait for them, while the own region
+			// (and the face ghosts) is read by this wave's own Z stage only, whose LDS
+			// reads come after these writes anyway.
+			if (edge) {
+#pragma unroll
+				for (int t = 0; t < 2; t++)
+#pragma unroll
+					for (int j = 0; j < 9; j++)
+						if ((WMZ >> j) & 1u) egp[(t * NWZ + wslot(WMZ, j)) * BS] = yv[t][j];
+			}
+			// edges in LDS before the counter says so (LDS only: global memory keeps flowing)
+			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+			__hip_atomic_store(&rdy[wv], it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			asm volatile("" ::: "memory");
 #pragma unroll
 			for (int t = 0; t < 2; t++)
 #pragma unroll
 				for (int j = 0; j < 9; j++)
-					if ((WMZ >> j) & 1u) {
-						const int q = wslot(WMZ, j);
-						rg[wv][t][q][rs0] = yv[t][j];
-						if (edge) egp[(t * NWZ + q) * BS] = yv[t][j];
-					}
+					if ((WMZ >> j) & 1u) rg[wv][t][wslot(WMZ, j)][rs0] = yv[t][j];
 			if constexpr (FACES)  // z ghosts: wave 0's left halo, the last wave's right halo
 				z_ghosts(y, yv, [&](int side, int t, int q, double v) {
 					if (side == 0) rg[0][t][q][rs(-z)] = v;
 					else rg[NW - 1][t][q][rs(2 * ((ZS ? ZT : Z) - 1) - z - 64 * (NW - 1))] = v;
 				});
-			// edges in LDS before the counter says so (LDS only: global memory keeps flowing)
-			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-			__hip_atomic_store(&rdy[wv], it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 		} else {
 			__syncthreads();  // every wave has finished reading zl (previous row's Z stage)
 #pragma unroll
@@ -978,18 +1010,17 @@ __global__ __launch_bounds__(ZT, kTx2MinWaves) void k_step_tx2(
 				__builtin_amdgcn_s_sleep(1);  // a neighbour wave's edges are not there yet
 			}
 			asm volatile("" ::: "memory");
-			if (ln < BS && wv > 0) {
-#pragma unroll
-				for (int t = 0; t < 2; t++)
-#pragma unroll
-					for (int q = 0; q < NWZ; q++) rg[wv][t][q][rs(ln - BS)] = eg[es][wv - 1][1][t][q][ln];
-			}
-			if (ln >= 64 - BS && wv < NW - 1) {
-#pragma unroll
-				for (int t = 0; t < 2; t++)
-#pragma unroll
-					for (int q = 0; q < NWZ; q++) rg[wv][t][q][rs(ln + BS)] = eg[es][wv + 1][0][t][q][ln - (64 - BS)];
-			}
+			// One edge value per hand-over lane, both sides in one LDS read and one
+			// write (hpk above, unpacked here each row).  Ordering: the flags and the ring are as they
+			// were -- a neighbour's edges of row `it` are in `eg` before its counter
+			// says so, and it overwrites this ring row only at row it + 2, after its
+			// collect of row it + 1 has seen this wave's counter at it + 1, which this
+			// wave sets after the read below has returned (publish's lgkmcnt(0)).
+			// Which lanes copy does not matter to the Z stage: the same wave does
+			// the copy and the Z-stage reads of its halo, and a wave's LDS operations
+			// complete in order.
+			const unsigned p = opaque_u32(hpk);
+			if ((int)p >= 0) (&rg[0][0][0][0])[p >> 16] = (&eg[0][0][0][0][0][0])[(p & 0xFFFFu) + (unsigned)(es * ESZ)];
 			asm volatile("" ::: "memory");
 		}
 	};
