@@ -21,6 +21,7 @@
 #include "launch.hpp"
 #include "ortho.hpp"
 #include "acoustic.hpp"
+#include "observe.hpp"
 #include "plan.hpp"
 
 using namespace gcmx;
@@ -191,6 +192,20 @@ struct gcmx_ctx {
 	int* nodes_d = nullptr;
 	size_t nodes_cap = 0;
 	double* ode_d = nullptr;  // per-material ODE factors (256)
+	// observation calls (gcmx_gather, gcmx_snapshot_box, gcmx_scan): device staging
+	// of their outputs, grown to the largest request
+	void* obs_d = nullptr;
+	size_t obs_cap = 0;
+	// bytes the layer and observation calls copied (gcmx_transfer_stats)
+	uint64_t bytes_d2h = 0, bytes_h2d = 0;
+};
+
+// Inner nodes of a context as element offsets of its layout (gcmx_node_list_create).
+struct gcmx_node_list {
+	gcmx_ctx* ctx = nullptr;
+	int device = 0;
+	long long n = 0;
+	long long* off_d = nullptr;
 };
 
 struct gcmx_border_nodes {
@@ -1439,6 +1454,7 @@ void gcmx_destroy(gcmx_ctx* c) {
 	(void)hipFree(c->mat_d);
 	(void)hipFree(c->nodes_d);
 	(void)hipFree(c->ode_d);
+	(void)hipFree(c->obs_d);
 	(void)hipFree(c->het_d);
 	(void)hipFree(c->ortho_het_d);
 	if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
@@ -1590,6 +1606,7 @@ gcmx_status gcmx_upload(gcmx_ctx* c, const double* aos) {
 	}
 	if ((s = wait_stream(c, c->stream, "gcmx_upload")) != GCMX_OK) return s;
 	HIP_TRY(hipMemcpy(c->cur, soa.data(), c->layer_elems * sizeof(double), hipMemcpyHostToDevice));
+	c->bytes_h2d += c->layer_elems * sizeof(double);
 	touch_layer(c);
 	return GCMX_OK;
 }
@@ -1603,6 +1620,7 @@ gcmx_status gcmx_download(gcmx_ctx* c, double* aos) {
 	std::vector<double> soa(c->layer_elems);
 	if ((s = wait_stream(c, c->stream, "gcmx_download")) != GCMX_OK) return s;
 	HIP_TRY(hipMemcpy(soa.data(), c->cur, c->layer_elems * sizeof(double), hipMemcpyDeviceToHost));
+	c->bytes_d2h += c->layer_elems * sizeof(double);
 	soa_to_aos(c, soa.data(), aos);
 	return GCMX_OK;
 }
@@ -1623,6 +1641,193 @@ gcmx_status gcmx_fill_random(gcmx_ctx* c, const int gs[3], uint64_t seed) {
 	launch_fill_random(c->cur, c->geo, st, D > 1 ? gs[1] : 1, D > 2 ? gs[2] : 1, seed, c->stream);
 	HIP_TRY(hipGetLastError());
 	touch_layer(c);
+	return GCMX_OK;
+}
+
+// ---- observation (observe.hpp) -------------------------------------------------
+
+namespace {
+
+// Quantity codes of an observation call -> ObserveQ: the PhysicalQuantities codes
+// the border calls take and GCMX_Q_COMPONENT(c); a code the context's model and
+// dimension do not have is refused.
+gcmx_status observe_q(const gcmx_ctx* c, int n_q, const int* qs, int min_q, ObserveQ& oq) {
+	if (n_q < min_q || n_q > kMaxBorderQ || (n_q > 0 && !qs))
+		return fail(GCMX_ERR_INVALID_ARG, "bad quantity list (at most 16)");
+	oq.n = n_q;
+	oq.D = c->D;
+	for (int d = 0; d < 3; d++) oq.diag[d] = d < c->D ? quantity_comp(c->D, d == 0 ? 5 : d == 1 ? 8 : 10) : 0;
+	for (int k = 0; k < kMaxBorderQ; k++) oq.comp[k] = 0;
+	for (int k = 0; k < n_q; k++) {
+		const int q = qs[k];
+		int comp = -2;
+		if (q >= GCMX_Q_COMPONENT(0)) {
+			if (q - GCMX_Q_COMPONENT(0) < c->M) comp = q - GCMX_Q_COMPONENT(0);
+		} else if (c->model == GCMX_MODEL_ACOUSTIC) {
+			if (q >= 2 && q <= 4 && q - 2 < c->D) comp = q - 2;
+			if (q == 12) comp = c->D;
+		} else if (q == 12) {
+			comp = kObservePressure;
+		} else if (q >= 2 && q <= 10) {
+			const int e = quantity_comp(c->D, q);
+			if (e >= 0) comp = e;
+		}
+		if (comp == -2) return fail(GCMX_ERR_INVALID_ARG, "quantity not in this context's PDE vector");
+		oq.comp[k] = comp;
+	}
+	return GCMX_OK;
+}
+
+// The context's staging holds at least `bytes`.  The observation calls are
+// synchronous, so nothing on the stream still uses the old block.
+gcmx_status observe_staging(gcmx_ctx* c, size_t bytes) {
+	if (bytes <= c->obs_cap) return GCMX_OK;
+	(void)hipFree(c->obs_d);
+	c->obs_d = nullptr;
+	c->obs_cap = 0;
+	if (hipMalloc(&c->obs_d, bytes) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(GCMX_ERR_OOM, "device staging allocation failed");
+	}
+	c->obs_cap = bytes;
+	return GCMX_OK;
+}
+
+// The stream's work done, then `bytes` of the staging at `offset` into `dst`.
+gcmx_status observe_fetch(gcmx_ctx* c, void* dst, size_t offset, size_t bytes) {
+	HIP_TRY(hipMemcpy(dst, static_cast<const char*>(c->obs_d) + offset, bytes, hipMemcpyDeviceToHost));
+	c->bytes_d2h += bytes;
+	return GCMX_OK;
+}
+
+}  // namespace
+
+gcmx_status gcmx_node_list_create(gcmx_ctx* c, int n_nodes, const int* nodes, gcmx_node_list** out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	*out = nullptr;
+	if (n_nodes < 1 || !nodes) return fail(GCMX_ERR_INVALID_ARG, "a node list needs at least one node");
+	const int D = c->D;
+	std::vector<long long> off((size_t)n_nodes);
+	for (int i = 0; i < n_nodes; i++) {
+		int it[3] = {0, 0, 0};
+		for (int d = 0; d < D; d++) {
+			it[d] = nodes[(size_t)i * D + d];
+			if (it[d] < 0 || it[d] >= c->geo.sizes[d]) return fail(GCMX_ERR_INVALID_ARG, "node outside the inner box");
+		}
+		off[(size_t)i] = dev_offset(c->geo, it);
+	}
+	auto* h = new gcmx_node_list();
+	h->ctx = c;
+	h->device = c->device;
+	h->n = n_nodes;
+	const size_t bytes = off.size() * sizeof(long long);
+	if (hipMalloc(&h->off_d, bytes) != hipSuccess) {
+		(void)hipGetLastError();
+		delete h;
+		return fail(GCMX_ERR_OOM, "device allocation failed");
+	}
+	if (hipMemcpy(h->off_d, off.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+		(void)hipFree(h->off_d);
+		delete h;
+		return fail(GCMX_ERR_HIP, "node list upload failed");
+	}
+	c->bytes_h2d += bytes;
+	*out = h;
+	return GCMX_OK;
+}
+
+void gcmx_node_list_destroy(gcmx_node_list* h) {
+	if (!h) return;
+	// hipFree waits for the device, so a gather that still reads the list is done;
+	// the context is not touched (it may be gone already)
+	(void)hipSetDevice(h->device);
+	(void)hipFree(h->off_d);
+	delete h;
+}
+
+gcmx_status gcmx_gather(gcmx_ctx* c, const gcmx_node_list* h, int n_q, const int* qs, double* out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!h || h->ctx != c) return fail(GCMX_ERR_INVALID_ARG, "node list of another context");
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	ObserveQ oq;
+	if ((s = observe_q(c, n_q, qs, 1, oq)) != GCMX_OK) return s;
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	const size_t bytes = (size_t)h->n * n_q * sizeof(double);
+	if ((s = observe_staging(c, bytes)) != GCMX_OK) return s;
+	{
+		Timed t(c, "gather_q", (double)bytes * 2, c->stream);
+		launch_gather_q(c->cur, c->geo, h->n, h->off_d, oq, static_cast<double*>(c->obs_d), c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	if ((s = wait_stream(c, c->stream, "gcmx_gather")) != GCMX_OK) return s;
+	return observe_fetch(c, out, 0, bytes);
+}
+
+gcmx_status gcmx_snapshot_box(gcmx_ctx* c, const int bmin_[3], const int bmax_[3], int want_velocity, int n_q,
+                              const int* qs, float* velocity, float* out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!bmin_ || !bmax_) return fail(GCMX_ERR_INVALID_ARG, "null box");
+	int bmin[3] = {0, 0, 0}, bmax[3] = {1, 1, 1};
+	long long n = 1;
+	for (int d = 0; d < c->D; d++) {
+		bmin[d] = bmin_[d];
+		bmax[d] = bmax_[d];
+		if (bmin[d] < 0 || bmax[d] > c->geo.sizes[d]) return fail(GCMX_ERR_INVALID_ARG, "box outside the inner nodes");
+		if (bmax[d] <= bmin[d]) return fail(GCMX_ERR_INVALID_ARG, "empty box");
+		n *= bmax[d] - bmin[d];
+	}
+	ObserveQ oq;
+	if ((s = observe_q(c, n_q, qs, 0, oq)) != GCMX_OK) return s;
+	if (!want_velocity && n_q == 0) return fail(GCMX_ERR_INVALID_ARG, "neither Velocity nor a quantity asked for");
+	if ((want_velocity && !velocity) || (n_q > 0 && !out)) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	const size_t vel_bytes = want_velocity ? (size_t)n * 3 * sizeof(float) : 0;
+	const size_t q_bytes = (size_t)n * n_q * sizeof(float);
+	if ((s = observe_staging(c, vel_bytes + q_bytes)) != GCMX_OK) return s;
+	float* vel_d = want_velocity ? static_cast<float*>(c->obs_d) : nullptr;
+	float* q_d = reinterpret_cast<float*>(static_cast<char*>(c->obs_d) + vel_bytes);
+	{
+		// algorithmic bytes: the fp64 planes read (Velocity's D, a trace's D, else 1) and the Float32 written
+		double planes = want_velocity ? c->D : 0;
+		for (int k = 0; k < n_q; k++) planes += oq.comp[k] == kObservePressure ? c->D : 1;
+		Timed t(c, "pack_vtk", (double)n * planes * sizeof(double) + (double)(vel_bytes + q_bytes), c->stream);
+		launch_pack_vtk(c->cur, c->geo, bmin, bmax, vel_d, oq, q_d, c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	if ((s = wait_stream(c, c->stream, "gcmx_snapshot_box")) != GCMX_OK) return s;
+	if (want_velocity && n_q > 0 && out == velocity + (size_t)n * 3) return observe_fetch(c, velocity, 0, vel_bytes + q_bytes);
+	if (want_velocity && (s = observe_fetch(c, velocity, 0, vel_bytes)) != GCMX_OK) return s;
+	if (n_q > 0 && (s = observe_fetch(c, out, vel_bytes, q_bytes)) != GCMX_OK) return s;
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_scan(gcmx_ctx* c, gcmx_scan_result* out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	const size_t bytes = kScanWords * sizeof(unsigned long long);
+	static_assert(sizeof(gcmx_scan_result) == kScanWords * sizeof(unsigned long long), "gcmx_scan_result is the kernel's words");
+	if ((s = observe_staging(c, bytes)) != GCMX_OK) return s;
+	{
+		Timed t(c, "scan", (double)c->geo.n_inner * c->M * sizeof(double), c->stream);
+		launch_scan(c->cur, c->geo, static_cast<unsigned long long*>(c->obs_d), c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	if ((s = wait_stream(c, c->stream, "gcmx_scan")) != GCMX_OK) return s;
+	// word 1 + k holds the bit pattern of max |v| of component k
+	return observe_fetch(c, out, 0, bytes);
+}
+
+gcmx_status gcmx_transfer_stats(gcmx_ctx* c, uint64_t out[2]) {
+	if (!c) return fail(GCMX_ERR_INVALID_ARG, "null context");
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	out[0] = c->bytes_d2h;
+	out[1] = c->bytes_h2d;
 	return GCMX_OK;
 }
 

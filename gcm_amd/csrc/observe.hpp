@@ -1,0 +1,43 @@
+// observe.hpp -- launchers of the observation kernels (kernels_observe.hip):
+// what a snapshotter or a detector needs from the current layer, formed on the
+// device so that no call moves a whole layer to the host.
+//   k_gather_q  quantities at listed nodes                 (gcmx_gather)
+//   k_pack_vtk  the Float32 arrays of a box, VTK order     (gcmx_snapshot_box)
+//   k_scan      non-finite count and max |v| per component (gcmx_scan)
+// Quantities are getQuantityOf's (host/task.hpp:134-143, host/acoustic_model.hpp:
+// 145-180), bitwise: a component itself, or the elastic PRESSURE
+//   trace = 0.0; trace += s_00; trace += s_11; ...; -trace / (double)D.
+#pragma once
+
+#include "common.hpp"
+#include "launch.hpp"
+
+namespace gcmx {
+
+// Quantities of one observation call, by value (kernel arguments).
+struct ObserveQ {
+	int n;                  // quantities, <= kMaxBorderQ
+	int comp[kMaxBorderQ];  // the component a quantity names, or kObservePressure
+	int D;                  // terms of the elastic pressure's trace
+	int diag[3];            // components of s_00, s_11, s_22
+};
+constexpr int kObservePressure = -1;
+
+// out[q][i] = quantity q at element offset off_d[i] (origin included) of `cur`.
+void launch_gather_q(const double* cur, const Geo& g, long long n, const long long* off_d,
+                     const ObserveQ& oq, double* out_d, hipStream_t st);
+
+// The inner box [bmin, bmax) of `cur` as Float32 in VTK point order (x fastest,
+// then y, then z): vel_d[n][3] when non-null (components >= D are 0.0f), then
+// q_d[oq.n][n].  2-D and 3-D transpose through an LDS tile (the layer's fastest
+// axis is the VTK order's slowest); 1-D copies.
+void launch_pack_vtk(const double* cur, const Geo& g, const int bmin[3], const int bmax[3],
+                     float* vel_d, const ObserveQ& oq, float* q_d, hipStream_t st);
+
+// res_d[0] = number of non-finite component values over the inner nodes (64-bit),
+// res_d[1 + c] = bits of max |v| over the finite values of component c (0.0 when
+// none).  Zeroes res_d on the stream first.
+constexpr int kScanWords = 1 + kMaxM;
+void launch_scan(const double* cur, const Geo& g, unsigned long long* res_d, hipStream_t st);
+
+}  // namespace gcmx

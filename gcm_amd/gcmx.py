@@ -35,11 +35,20 @@ MAX_BORDER_Q = 16
 QUANTITY_CODES = {"Vx": 2, "Vy": 3, "Vz": 4, "Sxx": 5, "Sxy": 6, "Sxz": 7, "Syy": 8, "Syz": 9,
                   "Szz": 10, "PRESSURE": 12}
 
+
+def Q_COMPONENT(c: int) -> int:
+    """GCMX_Q_COMPONENT(c): the quantity code of component c of the PDE vector itself
+    (the observation calls: gather, snapshot_box)."""
+    return 64 + int(c)
+
 # Exported symbols, in header order (checked by tests/test_abi.py).
 SYMBOLS = [
     "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_model_pde_size", "gcmx_status_string",
     "gcmx_create", "gcmx_create_model", "gcmx_get_model", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
-    "gcmx_upload", "gcmx_download", "gcmx_fill_random", "gcmx_stage", "gcmx_step",
+    "gcmx_upload", "gcmx_download", "gcmx_fill_random",
+    "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_scan",
+    "gcmx_transfer_stats",
+    "gcmx_stage", "gcmx_step",
     "gcmx_set_kernel_path", "gcmx_set_step_schedule", "gcmx_set_fp_mode", "gcmx_get_fp_mode", "gcmx_effective_path", "gcmx_last_step_path",
     "gcmx_border_fill",
     "gcmx_border_nodes_create", "gcmx_border_apply", "gcmx_border_nodes_destroy", "gcmx_step_faces",
@@ -82,6 +91,11 @@ class CommOptions(ctypes.Structure):
     """gcmx_comm_options."""
     _fields_ = [("global_x", ctypes.c_int), ("channels_per_peer", ctypes.c_int),
                 ("min_ctas", ctypes.c_int), ("max_ctas", ctypes.c_int), ("timeout_s", ctypes.c_double)]
+
+
+class ScanResult(ctypes.Structure):
+    """gcmx_scan_result."""
+    _fields_ = [("nonfinite", ctypes.c_uint64), ("max_abs", ctypes.c_double * 9)]
 
 
 class GridDesc(ctypes.Structure):
@@ -128,6 +142,18 @@ def lib() -> ctypes.CDLL:
     L.gcmx_upload.argtypes = [vp, dp]
     L.gcmx_download.argtypes = [vp, dp]
     L.gcmx_fill_random.argtypes = [vp, ip, ctypes.c_uint64]
+    # (the observation calls: bound when present, like the round-5 additions below,
+    # so that A/B timing runs can load an older build; tests/test_abi.py checks
+    # this build exports them)
+    if hasattr(L, "gcmx_snapshot_box"):
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.gcmx_node_list_create.argtypes = [vp, ctypes.c_int, ip, ctypes.POINTER(vp)]
+        L.gcmx_node_list_destroy.argtypes = [vp]
+        L.gcmx_node_list_destroy.restype = None
+        L.gcmx_gather.argtypes = [vp, vp, ctypes.c_int, ip, dp]
+        L.gcmx_snapshot_box.argtypes = [vp, ip, ip, ctypes.c_int, ctypes.c_int, ip, fp, fp]
+        L.gcmx_scan.argtypes = [vp, ctypes.POINTER(ScanResult)]
+        L.gcmx_transfer_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.gcmx_stage.argtypes = [vp, ctypes.c_int, ctypes.c_double]
     L.gcmx_step.argtypes = [vp, ctypes.c_double]
     L.gcmx_set_kernel_path.argtypes = [vp, ctypes.c_int]
@@ -320,6 +346,49 @@ class Context:
         out = np.empty((self.n_all, self.M))
         _check(lib().gcmx_download(self._ptr, _dp(out)))
         return out
+
+    # -- observation (no layer leaves the device) ---------------------------
+    def node_list(self, nodes: np.ndarray) -> "NodeList":
+        """gcmx_node_list_create: a device-resident list of inner nodes [n, dim]."""
+        return NodeList(self, nodes)
+
+    def gather(self, node_list: "NodeList", quantities: Sequence[int]) -> np.ndarray:
+        """gcmx_gather: [n_q, n] float64, quantity codes QUANTITY_CODES / Q_COMPONENT(c)."""
+        out = np.empty((len(quantities), node_list.n))
+        _check(lib().gcmx_gather(self._ptr, node_list.ptr, len(quantities), _ip(quantities), _dp(out)))
+        return out
+
+    def snapshot_box(self, box_min: Sequence[int], box_max: Sequence[int], quantities: Sequence[int],
+                     velocity: bool = True):
+        """gcmx_snapshot_box: the Float32 arrays of the inner box [box_min, box_max)
+        in VTK point order (x fastest).  Returns (velocity [n, 3] or None,
+        values [n_q, n])."""
+        pad = lambda v, fill: list(v)[:self.dim] + [fill] * (3 - self.dim)
+        lo, hi = pad(box_min, 0), pad(box_max, 1)
+        n = int(np.prod([max(0, b - a) for a, b in zip(lo, hi)]))
+        fp = ctypes.POINTER(ctypes.c_float)
+        # one block, Velocity first: the call then makes one device -> host copy
+        buf = np.empty(max(1, n * ((3 if velocity else 0) + len(quantities))), dtype=np.float32)
+        vel = buf[:3 * n].reshape(n, 3) if velocity else None
+        q = buf[(3 * n if velocity else 0):][:n * len(quantities)].reshape(len(quantities), n)
+        _check(lib().gcmx_snapshot_box(self._ptr, _ip(lo), _ip(hi), 1 if velocity else 0, len(quantities),
+                                       _ip(quantities), vel.ctypes.data_as(fp) if velocity else None,
+                                       q.ctypes.data_as(fp) if len(quantities) else None))
+        return vel, q
+
+    def scan(self):
+        """gcmx_scan: (number of non-finite inner component values, max |v| of the
+        finite values per component [M])."""
+        r = ScanResult()
+        _check(lib().gcmx_scan(self._ptr, ctypes.byref(r)))
+        return int(r.nonfinite), np.array(r.max_abs[:self.M])
+
+    def transfer_bytes(self):
+        """gcmx_transfer_stats: (bytes device -> host, bytes host -> device) copied
+        since the context was created."""
+        out = (ctypes.c_uint64 * 2)()
+        _check(lib().gcmx_transfer_stats(self._ptr, out))
+        return int(out[0]), int(out[1])
 
     def fill_random(self, global_sizes: Sequence[int], seed: int):
         gs = list(global_sizes) + [1] * (3 - len(global_sizes))
@@ -583,6 +652,31 @@ class BorderNodes:
     def close(self):
         if self.ptr and self.ptr.value and self._ctx.ptr.value:
             lib().gcmx_border_nodes_destroy(self.ptr)
+        self.ptr = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NodeList:
+    """gcmx_node_list: inner nodes uploaded once, gathered any number of times."""
+
+    def __init__(self, ctx: Context, nodes: np.ndarray):
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, ctx.dim)
+        self.ptr = ctypes.c_void_p()
+        self.n = nodes.shape[0]
+        self._ctx = ctx  # keeps the context alive
+        _check(lib().gcmx_node_list_create(ctx.ptr, nodes.shape[0],
+                                           nodes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                           ctypes.byref(self.ptr)))
+        ctx._adopt(self)
+
+    def close(self):
+        if self.ptr and self.ptr.value:
+            lib().gcmx_node_list_destroy(self.ptr)
         self.ptr = ctypes.c_void_p()
 
     def __del__(self):

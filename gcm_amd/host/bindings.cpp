@@ -142,6 +142,12 @@ struct PyEngine {
 		}
 		return out;
 	}
+	/// Bytes the body's context copied (device -> host, host -> device): gcmx_transfer_stats.
+	std::pair<uint64_t, uint64_t> transferBytes(size_t id) {
+		uint64_t v[2] = {0, 0};
+		gcmxCheck(gcmx_transfer_stats(ctxOf(id), v), "gcmx_transfer_stats");
+		return {v[0], v[1]};
+	}
 	real maximalEigenvalue(size_t id) {
 		if (D == 1) return as<1>().getMesh(id)->getMaximalEigenvalue();
 		if (D == 2) return as<2>().getMesh(id)->getMaximalEigenvalue();
@@ -185,6 +191,37 @@ void writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::
 	cubic::writeVtkSnapshot<D>(fileName, grid.sizes, grid.start, grid.h, grid.borderSize,
 	                           layer.data(), st.matId.data(), st.materialNumber,
 	                           task.vtkSnapshotter.quantitiesToSnap, st.model);
+}
+
+/// The array loop of the GPU-free VtkSnapshotter alone (cubic::vtkLayerArrays): the
+/// Float32 "Velocity" and quantity arrays of a layer given in the reference AoS
+/// all-nodes order, as numpy arrays that own the vectors (no copy).
+template <int D>
+py::dict vtkLayerArraysHost(const std::vector<int>& sizes, int borderSize, py::array_t<real, py::array::c_style> pde,
+                            const std::vector<std::string>& quantities, bool acoustic) {
+	std::array<int, D> sz;
+	size_t all = 1;
+	for (int i = 0; i < D; i++) {
+		sz[i] = sizes.at((size_t)i);
+		all *= (size_t)(sz[i] + 2 * borderSize);
+	}
+	const Models::T model = acoustic ? Models::T::ACOUSTIC : Models::T::ELASTIC;
+	if ((size_t)pde.size() != all * (size_t)pdeSizeOf(model, D)) throw Exception("vtk_layer_arrays: pde has the wrong size");
+	std::vector<PhysicalQuantities::T> qs;
+	for (const auto& q : quantities) qs.push_back(quantity(q));
+	cubic::VtsArray vel;
+	std::vector<cubic::VtsArray> arrays;
+	cubic::vtkLayerArrays<D>(sz, borderSize, pde.data(), qs, model, vel, arrays);
+	auto adopt = [](std::vector<float>&& v, std::vector<ssize_t> shape) {
+		auto* heap = new std::vector<float>(std::move(v));
+		py::capsule owner(heap, [](void* p) { delete static_cast<std::vector<float>*>(p); });
+		return py::array_t<float>(shape, heap->data(), owner);
+	};
+	py::dict d;
+	const ssize_t n = (ssize_t)(vel.values.size() / 3);
+	d[py::str(vel.name)] = adopt(std::move(vel.values), {n, (ssize_t)3});
+	for (auto& a : arrays) d[py::str(a.name)] = adopt(std::move(a.values), {n});
+	return d;
 }
 
 /// One body of the GPU-free simplex set-up (simplex::buildHostPlans) as numpy arrays.
@@ -391,6 +428,8 @@ PYBIND11_MODULE(_gcm_host, m) {
 		         t.vtkSnapshotter.quantitiesToSnap.clear();
 		         for (auto& q : qs) t.vtkSnapshotter.quantitiesToSnap.push_back(quantity(q));
 	         })
+	    .def("set_vtk_chunk_bytes", [](Task& t, size_t bytes) { t.vtkSnapshotter.chunkBytes = bytes; },
+	         "most output bytes one device request of the cubic VtkSnapshotter carries (default 256 MiB)")
 	    .def("set_detector",
 	         [](Task& t, std::vector<std::string> qs, py::tuple area, size_t gridId) {
 		         t.detector.quantities.clear();
@@ -547,6 +586,20 @@ PYBIND11_MODULE(_gcm_host, m) {
 	    },
 	    "GPU-free VtkSnapshotter file of one body (set-up layer, or `pde`)", py::arg("task"),
 	    py::arg("body_id"), py::arg("file_name"), py::arg("pde") = py::none());
+
+	m.def(
+	    "vtk_layer_arrays",
+	    [](const std::vector<int>& sizes, int borderSize, py::array_t<real, py::array::c_style> pde,
+	       const std::vector<std::string>& quantities, const std::string& model) {
+		    if (model != "elastic" && model != "acoustic") throw Exception("model must be elastic or acoustic");
+		    const bool ac = model == "acoustic";
+		    if (sizes.size() == 1) return vtkLayerArraysHost<1>(sizes, borderSize, pde, quantities, ac);
+		    if (sizes.size() == 2) return vtkLayerArraysHost<2>(sizes, borderSize, pde, quantities, ac);
+		    if (sizes.size() == 3) return vtkLayerArraysHost<3>(sizes, borderSize, pde, quantities, ac);
+		    throw Exception("dimensionality must be 1, 2 or 3");
+	    },
+	    "GPU-free VtkSnapshotter array loop: Float32 Velocity and quantity arrays (VTK order) of an all-nodes layer",
+	    py::arg("sizes"), py::arg("border_size"), py::arg("pde"), py::arg("quantities"), py::arg("model") = "elastic");
 
 	m.def(
 	    "write_simplex_vtk",
@@ -720,6 +773,8 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         "per-kernel timing of the body's context (gcmx_profile_enable)")
 	    .def("profile_kernels", &PyEngine::profileKernels, py::arg("body") = 0,
 	         "kernel instances the body's profiled launches ran (gcmx_profile_kernel)")
+	    .def("transfer_bytes", &PyEngine::transferBytes, py::arg("body") = 0,
+	         "bytes the body's context copied (device -> host, host -> device) since it was created")
 	    .def("maximal_eigenvalue", &PyEngine::maximalEigenvalue)
 	    .def_property_readonly("steps", [](PyEngine& p) { return p.e->stepsDone(); })
 	    .def_property_readonly("required_time", [](PyEngine& p) { return p.e->getRequiredTime(); })

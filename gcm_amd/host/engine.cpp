@@ -468,12 +468,59 @@ std::vector<real> HipMesh<D>::pdeAll() const {
 
 template <int D>
 std::array<real, HipMesh<D>::M> HipMesh<D>::pde(const IntD& it) const {
-	const std::vector<real> all = pdeAll();
-	std::array<real, M> v{};
-	const size_t i = (size_t)this->getIndex(it);
 	const int m = pdeM();
-	for (int c = 0; c < m; c++) v[c] = all[i * m + c];
+	std::vector<int> components;
+	for (int c = 0; c < m; c++) components.push_back(GCMX_Q_COMPONENT(c));
+	const std::vector<real> got = gather(*nodeList({it}), components);
+	std::array<real, M> v{};
+	for (int c = 0; c < m; c++) v[c] = got[(size_t)c];
 	return v;
+}
+
+// -------------------------------------------------------------- observation --
+
+template <int D>
+std::shared_ptr<typename HipMesh<D>::NodeList> HipMesh<D>::nodeList(const std::vector<IntD>& nodes) const {
+	std::vector<int> flat;
+	flat.reserve(nodes.size() * D);
+	for (const IntD& it : nodes)
+		for (int d = 0; d < D; d++) {
+			if (it[d] < 0 || it[d] >= this->sizes[d]) throw Exception("nodeList: only inner nodes can be observed");
+			flat.push_back(it[d] + (stack_ && d == stackAxis_ ? stackOffset_ : 0));
+		}
+	auto list = std::make_shared<NodeList>();
+	gcmxCheck(gcmx_node_list_create(ctx_, (int)nodes.size(), flat.data(), &list->handle), "gcmx_node_list_create");
+	list->size = nodes.size();
+	return list;
+}
+
+template <int D>
+std::vector<real> HipMesh<D>::gather(const NodeList& nodes, const std::vector<int>& quantities) const {
+	std::vector<real> out(quantities.size() * nodes.size);
+	gcmxCheck(gcmx_gather(ctx_, nodes.handle, (int)quantities.size(), quantities.data(), out.data()), "gcmx_gather");
+	return out;
+}
+
+template <int D>
+void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const std::vector<int>& quantities,
+                                float* velocity, float* values) const {
+	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
+	for (int d = 0; d < D; d++) {
+		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("snapshotArrays: only inner nodes can be observed");
+		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
+		lo[d] = boxMin[d] + off;
+		hi[d] = boxMax[d] + off;
+	}
+	gcmxCheck(gcmx_snapshot_box(ctx_, lo, hi, velocity ? 1 : 0, (int)quantities.size(), quantities.data(), velocity,
+	                            values),
+	          "gcmx_snapshot_box");
+}
+
+template <int D>
+std::array<uint64_t, 2> HipMesh<D>::transferBytes() const {
+	uint64_t v[2] = {0, 0};
+	gcmxCheck(gcmx_transfer_stats(ctx_, v), "gcmx_transfer_stats");
+	return {v[0], v[1]};
 }
 
 // ----------------------------------------------------------------- the stage --
@@ -969,12 +1016,44 @@ template <int D>
 void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) {
 	const HipMesh<D>* mesh = dynamic_cast<const HipMesh<D>*>(mesh_);
 	if (!mesh) throw Exception("VtkSnapshotter: not a cubic mesh");
-	const std::vector<real> pde = mesh->pdeAll();  // the one device -> host copy
+	size_t n = 1;
+	for (int i = 0; i < D; i++) n *= (size_t)mesh->sizes[i];
+	VtsArray vel{"Velocity", 3, std::vector<float>(3 * n)};
+	std::vector<VtsArray> qs;
+	std::vector<int> codes;
+	for (auto q : quantitiesToSnap) {
+		if (!hasQuantityOf(mesh->model(), D, q)) throw Exception("quantity to snap is not in this PDE vector");
+		qs.push_back(VtsArray{quantityName(q), 1, std::vector<float>(n)});
+		codes.push_back(quantityCode(q));
+	}
+	// Slabs along the slowest VTK axis (the last one): whole lines and planes of the
+	// file's point order, so a slab's arrays are contiguous parts of the file's.
+	const int slow = D - 1;
+	const size_t plane = n / (size_t)mesh->sizes[slow];  // points per index of the slow axis
+	const size_t perPoint = 4 * (3 + qs.size());
+	const size_t thick = std::max<size_t>(1, chunkBytes / (plane * perPoint));
+	std::vector<float> slab;  // [quantities][points of the slab], when there are several
+	for (size_t s0 = 0; s0 < (size_t)mesh->sizes[slow]; s0 += thick) {
+		const size_t s1 = std::min<size_t>(s0 + thick, (size_t)mesh->sizes[slow]);
+		std::array<int, D> lo{}, hi = mesh->sizes;
+		lo[slow] = (int)s0;
+		hi[slow] = (int)s1;
+		const size_t first = s0 * plane, count = (s1 - s0) * plane;
+		float* values = nullptr;
+		if (qs.size() == 1) values = qs[0].values.data() + first;
+		if (qs.size() > 1) {
+			slab.resize(qs.size() * count);
+			values = slab.data();
+		}
+		mesh->snapshotArrays(lo, hi, codes, vel.values.data() + 3 * first, values);
+		if (qs.size() > 1)
+			for (size_t k = 0; k < qs.size(); k++)
+				std::copy(slab.begin() + k * count, slab.begin() + (k + 1) * count, qs[k].values.begin() + first);
+	}
 	const auto& ids = mesh->materialIdsAll();
-	writeVtkSnapshot<D>(makeFileNameForSnapshot(std::to_string(mesh->id), step, "vts", "vtk"),
-	                    mesh->sizes, mesh->start, mesh->h, mesh->borderSize, pde.data(),
-	                    ids.empty() ? nullptr : ids.data(), mesh->materialNumbers(),
-	                    quantitiesToSnap, mesh->model());
+	writeVtkArrays<D>(makeFileNameForSnapshot(std::to_string(mesh->id), step, "vts", "vtk"), mesh->sizes,
+	                  mesh->start, mesh->h, mesh->borderSize, ids.empty() ? nullptr : ids.data(),
+	                  mesh->materialNumbers(), std::move(vel), std::move(qs));
 }
 
 template <int D>
@@ -991,30 +1070,44 @@ template <int D>
 void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) {
 	const HipMesh<D>* mesh = dynamic_cast<const HipMesh<D>*>(mesh_);
 	if (!mesh) throw Exception("SliceSnapshotter: not a cubic mesh");
-	const int M = mesh->pdeM();
 	const int direction = D - 1;
-	const std::vector<real> pde = mesh->pdeAll();
-	auto at = [&](const std::array<int, D>& it) { return &pde[(size_t)mesh->getIndex(it) * M]; };
-	// along the last axis through sizes / 2 (SliceSnapshotter.hpp:45-63)
+	if (listsOf != mesh) {  // first use: the node lists go to the device once
+		column.reset();
+		detector.reset();
+		listsOf = mesh;
+		// along the last axis through sizes / 2 (SliceSnapshotter.hpp:45-63)
+		std::array<int, D> it;
+		for (int i = 0; i < D; i++) it[i] = mesh->sizes[i] / 2;
+		std::vector<std::array<int, D>> nodes;
+		for (int k = 0; k < mesh->sizes[direction]; k++) {
+			it[direction] = k;
+			nodes.push_back(it);
+		}
+		column = mesh->nodeList(nodes);
+		if (mesh->id == gridId) {
+			// upper detector: the right border of the last axis inside the area (hpp:65-88)
+			if (!hasQuantityOf(mesh->model(), D, quantityToWrite)) throw Exception("quantity not present in the PDE vector");
+			nodes.clear();
+			forEachInner<D>(mesh->sizes, [&](const std::array<int, D>& j) {
+				if (j[direction] != mesh->sizes[direction] - 1) return;
+				if (detectionArea->contains(mesh->coords(j))) nodes.push_back(j);
+			});
+			if (nodes.empty()) throw Exception("SliceSnapshotter: no node in the detection area");
+			detector = mesh->nodeList(nodes);
+		}
+	}
 	std::array<int, D> it;
 	for (int i = 0; i < D; i++) it[i] = mesh->sizes[i] / 2;
-	std::vector<real> coordZ, Vz;
+	std::vector<real> coordZ;
 	for (int k = 0; k < mesh->sizes[direction]; k++) {
 		it[direction] = k;
 		coordZ.push_back(mesh->coords(it)[direction]);
-		Vz.push_back(at(it)[direction]);
 	}
+	const std::vector<real> Vz = mesh->gather(*column, {quantityCode(PhysicalQuantities::T::Vx) + direction});
 	writeColumns(makeFileNameForSnapshot(std::to_string(mesh->id), step, "txt", "zaxis"),
 	             {coordZ, Vz});
 	if (mesh->id != gridId) return;
-	// upper detector: mean over the right border of the last axis (hpp:65-88)
-	std::vector<real> valuesInArea;
-	forEachInner<D>(mesh->sizes, [&](const std::array<int, D>& j) {
-		if (j[direction] != mesh->sizes[direction] - 1) return;
-		if (detectionArea->contains(mesh->coords(j)))
-			valuesInArea.push_back(getQuantityOf(mesh->model(), D, quantityToWrite, at(j)));
-	});
-	if (valuesInArea.empty()) throw Exception("SliceSnapshotter: no node in the detection area");
+	const std::vector<real> valuesInArea = mesh->gather(*detector, {quantityCode(quantityToWrite)});
 	real sum = 0;
 	for (real v : valuesInArea) sum += v;  // std::accumulate order
 	const real valueToWrite = sum / (real)valuesInArea.size();

@@ -168,9 +168,30 @@ public:
 	gcmx_ctx* ctx() const { return ctx_; }
 	/// Current layer in the reference AoS all-nodes order (downloads).
 	std::vector<real> pdeAll() const;
-	/// One node's PDE vector (downloads the layer; for tests and snapshots); an
+	/// One node's PDE vector (gathers its pdeM() components on the device); an
 	/// acoustic body fills the first pdeM() entries.
 	std::array<real, M> pde(const IntD& it) const;
+
+	/// OBSERVATION without a layer download (gcmx_gather / gcmx_snapshot_box).  Only
+	/// inner nodes are asked for; a stack member addresses the stack's context with
+	/// its own offset.  Quantities are PhysicalQuantities codes or GCMX_Q_COMPONENT(c).
+	struct NodeList {  ///< inner nodes uploaded once (gcmx_node_list)
+		gcmx_node_list* handle = nullptr;
+		size_t size = 0;
+		NodeList() = default;
+		NodeList(const NodeList&) = delete;
+		NodeList& operator=(const NodeList&) = delete;
+		~NodeList() { gcmx_node_list_destroy(handle); }
+	};
+	std::shared_ptr<NodeList> nodeList(const std::vector<IntD>& nodes) const;
+	/// [quantities][nodes] of the current layer.
+	std::vector<real> gather(const NodeList& nodes, const std::vector<int>& quantities) const;
+	/// The Float32 arrays of the inner box [boxMin, boxMax) in VTK point order (x
+	/// fastest): velocity[n][3] (null: not wanted) and values[quantities][n].
+	void snapshotArrays(const IntD& boxMin, const IntD& boxMax, const std::vector<int>& quantities,
+	                    float* velocity, float* values) const;
+	/// Bytes the body's context copied {device -> host, host -> device} (gcmx_transfer_stats).
+	std::array<uint64_t, 2> transferBytes() const;
 	int numberOfMaterials() const { return (int)(model_ == Models::T::ACOUSTIC ? acousticMatrices.size() : matrices.size()); }
 	/// tau0 of the materials in the device table order (gcmx_set_materials).
 	const std::vector<real>& deviceTau0() const { return deviceTau0_; }
@@ -314,13 +335,18 @@ template <int D>
 class VtkSnapshotter : public Snapshotter {
 public:
 	explicit VtkSnapshotter(const Task& task)
-	    : Snapshotter(task), quantitiesToSnap(task.vtkSnapshotter.quantitiesToSnap) {}
+	    : Snapshotter(task), quantitiesToSnap(task.vtkSnapshotter.quantitiesToSnap),
+	      chunkBytes(task.vtkSnapshotter.chunkBytes) {}
 
 protected:
+	/// The file's Velocity and quantity arrays come from the device already as
+	/// Float32 in VTK order (HipMesh::snapshotArrays), in slabs along the slowest VTK
+	/// axis of at most chunkBytes of output each.
 	void snapshotImpl(const AbstractGrid* mesh, const int step) override;
 
 private:
 	const std::vector<PhysicalQuantities::T> quantitiesToSnap;
+	const size_t chunkBytes;
 };
 
 /// SliceSnapshotter<Mesh> (util/snapshot/SliceSnapshotter.hpp:12-118): velocity
@@ -339,6 +365,10 @@ private:
 	std::vector<real> times, seismo;
 	std::shared_ptr<Area> detectionArea;
 	PhysicalQuantities::T quantityToWrite;
+	/// Made on first use, gathered at every snapshot: the column through sizes / 2
+	/// and the top-face nodes inside the detection area (forEachInner order).
+	const HipMesh<D>* listsOf = nullptr;
+	std::shared_ptr<typename HipMesh<D>::NodeList> column, detector;
 };
 
 /// engine/cubic/AbstractFactory.hpp:22-54

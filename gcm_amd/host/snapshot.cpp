@@ -205,30 +205,32 @@ void writeVts(const std::string& fileName, const int dims[3], const std::vector<
 	if (!f.good()) throw Exception("write failed: " + fileName);
 }
 
+// CubicGrid indexMaker (CubicGrid.hpp:202-225): X slowest, last axis fastest
 template <int D>
-void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& sizes,
-                      const std::array<int, D>& start, const std::array<real, D>& h,
-                      int borderSize, const real* pdeAll, const uint8_t* matIdAll,
-                      const std::vector<int>& materialNumbers,
-                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model) {
-	const int M = pdeSizeOf(model, D);
-	int dims[3] = {1, 1, 1};
-	for (int i = 0; i < D; i++) dims[i] = sizes[i];
-	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
-	// CubicGrid indexMaker (CubicGrid.hpp:202-225): X slowest, last axis fastest
-	long long im[3] = {0, 0, 0};
+static void indexMakerOf(const std::array<int, D>& sizes, int borderSize, long long im[3]) {
+	im[0] = im[1] = im[2] = 0;
 	const long long b2 = 2LL * borderSize;
 	if (D == 1) im[0] = 1;
 	if (D == 2) { im[0] = b2 + sizes[D - 1]; im[1] = 1; }
 	if (D == 3) { im[0] = (b2 + sizes[1 % D]) * (b2 + sizes[D - 1]); im[1] = b2 + sizes[D - 1]; im[2] = 1; }
-	std::vector<float> points(3 * n);
-	VtsArray vel{"Velocity", 3, std::vector<float>(3 * n)};
-	std::vector<VtsArray> qs;
+}
+
+template <int D>
+void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real* pdeAll,
+                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model, VtsArray& vel,
+                    std::vector<VtsArray>& qs) {
+	const int M = pdeSizeOf(model, D);
+	int dims[3] = {1, 1, 1};
+	for (int i = 0; i < D; i++) dims[i] = sizes[i];
+	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+	long long im[3];
+	indexMakerOf<D>(sizes, borderSize, im);
+	vel = VtsArray{"Velocity", 3, std::vector<float>(3 * n)};
+	qs.clear();
 	for (auto q : quantities) {
 		if (!hasQuantityOf(model, D, q)) throw Exception("quantity to snap is not in this PDE vector");
 		qs.push_back(VtsArray{quantityName(q), 1, std::vector<float>(n)});
 	}
-	VtsArray mat{"material_index", 1, std::vector<float>(n)};
 	// SlowZFastX (VtkIterator, CubicGrid.hpp:34): x fastest
 	size_t p = 0;
 	for (int z = 0; z < dims[2]; z++)
@@ -238,13 +240,35 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 				long long idx = 0;
 				for (int i = 0; i < D; i++) idx += im[i] * (it[i] + borderSize);
 				const real* v = pdeAll + (size_t)idx * M;
+				for (int i = 0; i < 3; i++) vel.values[3 * p + i] = i < D ? (float)v[i] : 0.0f;  // getVelocity, padded
+				for (size_t k = 0; k < qs.size(); k++)
+					qs[k].values[p] = (float)getQuantityOf(model, D, quantities[k], v);
+			}
+}
+
+template <int D>
+void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, const std::array<real, D>& h, int borderSize,
+                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers, VtsArray vel,
+                    std::vector<VtsArray> qs) {
+	int dims[3] = {1, 1, 1};
+	for (int i = 0; i < D; i++) dims[i] = sizes[i];
+	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+	long long im[3];
+	indexMakerOf<D>(sizes, borderSize, im);
+	std::vector<float> points(3 * n);
+	VtsArray mat{"material_index", 1, std::vector<float>(n)};
+	size_t p = 0;
+	for (int z = 0; z < dims[2]; z++)
+		for (int y = 0; y < dims[1]; y++)
+			for (int x = 0; x < dims[0]; x++, p++) {
+				const int it[3] = {x, y, z};
+				long long idx = 0;
+				for (int i = 0; i < D; i++) idx += im[i] * (it[i] + borderSize);
 				for (int i = 0; i < 3; i++) {
 					const real c = i < D ? (real)start[i] * h[i] + (real)it[i] * h[i] : 0;
 					points[3 * p + i] = (float)c;
-					vel.values[3 * p + i] = i < D ? (float)v[i] : 0.0f;  // getVelocity, padded
 				}
-				for (size_t k = 0; k < qs.size(); k++)
-					qs[k].values[p] = (float)getQuantityOf(model, D, quantities[k], v);
 				const int m = matIdAll ? matIdAll[idx] : 0;
 				mat.values[p] = (float)materialNumbers.at((size_t)m);
 			}
@@ -255,18 +279,34 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 	writeVts(fileName, dims, points, arrays);
 }
 
-template void writeVtkSnapshot<1>(const std::string&, const std::array<int, 1>&,
-                                  const std::array<int, 1>&, const std::array<real, 1>&, int,
-                                  const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&, Models::T);
-template void writeVtkSnapshot<2>(const std::string&, const std::array<int, 2>&,
-                                  const std::array<int, 2>&, const std::array<real, 2>&, int,
-                                  const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&, Models::T);
-template void writeVtkSnapshot<3>(const std::string&, const std::array<int, 3>&,
-                                  const std::array<int, 3>&, const std::array<real, 3>&, int,
-                                  const real*, const uint8_t*, const std::vector<int>&,
-                                  const std::vector<PhysicalQuantities::T>&, Models::T);
+template <int D>
+void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& sizes,
+                      const std::array<int, D>& start, const std::array<real, D>& h,
+                      int borderSize, const real* pdeAll, const uint8_t* matIdAll,
+                      const std::vector<int>& materialNumbers,
+                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model) {
+	VtsArray vel;
+	std::vector<VtsArray> qs;
+	vtkLayerArrays<D>(sizes, borderSize, pdeAll, quantities, model, vel, qs);
+	writeVtkArrays<D>(fileName, sizes, start, h, borderSize, matIdAll, materialNumbers, std::move(vel),
+	                  std::move(qs));
+}
+
+#define GCM_SNAPSHOT_INSTANCES(D)                                                                             \
+	template void vtkLayerArrays<D>(const std::array<int, D>&, int, const real*,                              \
+	                                const std::vector<PhysicalQuantities::T>&, Models::T, VtsArray&,          \
+	                                std::vector<VtsArray>&);                                                  \
+	template void writeVtkArrays<D>(const std::string&, const std::array<int, D>&, const std::array<int, D>&, \
+	                                const std::array<real, D>&, int, const uint8_t*, const std::vector<int>&, \
+	                                VtsArray, std::vector<VtsArray>);                                         \
+	template void writeVtkSnapshot<D>(const std::string&, const std::array<int, D>&,                          \
+	                                  const std::array<int, D>&, const std::array<real, D>&, int,             \
+	                                  const real*, const uint8_t*, const std::vector<int>&,                   \
+	                                  const std::vector<PhysicalQuantities::T>&, Models::T);
+GCM_SNAPSHOT_INSTANCES(1)
+GCM_SNAPSHOT_INSTANCES(2)
+GCM_SNAPSHOT_INSTANCES(3)
+#undef GCM_SNAPSHOT_INSTANCES
 
 }  // namespace cubic
 }  // namespace gcm

@@ -1,7 +1,9 @@
 // snapshot.hpp -- snapshotters of the cubic engine (util/snapshot/*.hpp).
 //
-// These are the device -> host sync points of a run: a snapshot downloads the
-// current layer once (HipMesh::pdeAll) and writes it on the host.
+// These are the device -> host sync points of a run.  A snapshot of the engine
+// asks the device for what its files hold (HipMesh::snapshotArrays / gather: the
+// Float32 arrays of the box, one column, one face) and writes it on the host;
+// the GPU-free writeVtkSnapshot builds the same arrays from a host layer.
 //   Snapshotter        (util/snapshot/Snapshotter.hpp:19-95)      -> gcm::Snapshotter
 //   VtkSnapshotter     (util/snapshot/VtkSnapshotter.hpp:12-86)   -> cubic::VtkSnapshotter<D>
 //   SliceSnapshotter   (util/snapshot/SliceSnapshotter.hpp:12-118)-> cubic::SliceSnapshotter<D>
@@ -122,6 +124,20 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
                       const std::vector<int>& materialNumbers,
                       const std::vector<PhysicalQuantities::T>& quantities,
                       Models::T model = Models::T::ELASTIC);
+
+/// The two halves of writeVtkSnapshot.  vtkLayerArrays: "Velocity" and the
+/// quantities' arrays of a layer in the reference AoS all-nodes order (the loop
+/// over the nodes in VTK order).  writeVtkArrays: the file from those arrays --
+/// the points and "material_index" are computed here from the grid and the ids.
+template <int D>
+void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real* pdeAll,
+                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model, VtsArray& velocity,
+                    std::vector<VtsArray>& quantityArrays);
+template <int D>
+void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, const std::array<real, D>& h, int borderSize,
+                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers, VtsArray velocity,
+                    std::vector<VtsArray> quantityArrays);
 
 const char* quantityName(PhysicalQuantities::T q);
 

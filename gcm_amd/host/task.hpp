@@ -309,6 +309,9 @@ struct Task {
 	struct VtkSnapshotter {
 		/// list of physical quantities to write to vtk
 		std::vector<PhysicalQuantities::T> quantitiesToSnap;
+		/// Host only: most output bytes one device -> host request of the cubic
+		/// VtkSnapshotter carries (it asks for the box in slabs of at most this).
+		size_t chunkBytes = 256u << 20;
 	} vtkSnapshotter;
 
 	struct Detector {

@@ -170,6 +170,58 @@ gcmx_status gcmx_download(gcmx_ctx* ctx, double* aos_all_nodes);
  * box of `global_sizes` nodes; ghosts untouched.  Generated on the device. */
 gcmx_status gcmx_fill_random(gcmx_ctx* ctx, const int global_sizes[3], uint64_t seed);
 
+/* ---- observation -------------------------------------------------------------
+ * What a snapshotter or a detector needs from the current layer, formed on the
+ * device: no call here moves a layer.  Replaces the reads of
+ * VtkSnapshotter::snapshotImpl (util/snapshot/VtkSnapshotter.hpp:20-61) and
+ * SliceSnapshotter::snapshotImpl (util/snapshot/SliceSnapshotter.hpp:37-90), which
+ * walk DefaultMesh::pde(it) on the host.
+ * Quantities: the PhysicalQuantities codes of gcmx_border_fill (2..4, 5..10, 12)
+ * and GCMX_Q_COMPONENT(c), component c of the PDE vector itself; a code the
+ * context's model and dimension do not have is GCMX_ERR_INVALID_ARG.  Values are
+ * bitwise the host's GetSetter::Get: a component, or, on an elastic context,
+ * PRESSURE = -trace / dim with trace = 0.0 + s_00 + s_11 + ... summed in that
+ * order and a true division (VelocitySigmaVariables.hpp:98-104); an acoustic
+ * context's PRESSURE is component dim.
+ * The three reading calls are synchronous like gcmx_download (a pending halo
+ * exchange and the stream's work complete first, the host buffers are filled on
+ * return), copy exactly their output bytes to the host, read the current layer
+ * and change no state of the context.  Device staging belongs to the context,
+ * grows to the largest request and is freed by gcmx_destroy. */
+#define GCMX_Q_COMPONENT(c) (64 + (c))
+/* A device-resident list of inner nodes (n_nodes x dim multi-indices, kept as
+ * element offsets): uploaded once, gathered any number of times.  A node outside
+ * the inner box is GCMX_ERR_INVALID_ARG.  The list belongs to the context it was
+ * created on. */
+typedef struct gcmx_node_list gcmx_node_list;
+gcmx_status gcmx_node_list_create(gcmx_ctx* ctx, int n_nodes, const int* nodes, gcmx_node_list** out);
+void        gcmx_node_list_destroy(gcmx_node_list* list);
+/* out[q][i] = quantity q at node i of the list; n_q in 1..GCMX_MAX_BORDER_Q. */
+gcmx_status gcmx_gather(gcmx_ctx* ctx, const gcmx_node_list* list, int n_q, const int* quantities,
+                        double* out);
+/* The Float32 arrays of the inner box [box_min, box_max) (entries >= dim are
+ * ignored) in VTK point order, n = the box's nodes with x fastest, then y, then z
+ * (VtkIterator, CubicGrid.hpp:34): velocity[n][3] when want_velocity (components
+ * >= dim are 0.0f) and out[n_q][n]; each value is (float) of the quantity's
+ * double, round to nearest even.  n_q in 0..GCMX_MAX_BORDER_Q; an empty box, a
+ * box outside the inner nodes, nothing asked for or a null buffer that is asked
+ * for is GCMX_ERR_INVALID_ARG.  Each of the two host buffers is filled by one
+ * copy (one copy for both when `out` follows `velocity` directly). */
+gcmx_status gcmx_snapshot_box(gcmx_ctx* ctx, const int box_min[3], const int box_max[3], int want_velocity,
+                              int n_q, const int* quantities, float* velocity, float* out);
+/* Health check of the current layer's inner nodes: the number of non-finite
+ * component values, and per component the maximum of |v| over the finite values
+ * (0.0 when there is none; entries >= M are 0.0).  Deterministic. */
+typedef struct gcmx_scan_result {
+	uint64_t nonfinite;
+	double   max_abs[9];
+} gcmx_scan_result;
+gcmx_status gcmx_scan(gcmx_ctx* ctx, gcmx_scan_result* out);
+/* out[0] / out[1]: bytes copied device -> host / host -> device since
+ * gcmx_create by gcmx_upload, gcmx_download and the observation calls (node
+ * lists included). */
+gcmx_status gcmx_transfer_stats(gcmx_ctx* ctx, uint64_t out[2]);
+
 /* ---- the hot path ------------------------------------------------------------
  * gcmx_stage replaces GridCharacteristicMethodBase::stage(s, timeStep, mesh)
  * (engine/cubic/GridCharacteristicMethod.hpp:13-17, impl :42-52) followed by
@@ -211,9 +263,10 @@ gcmx_status gcmx_stage(gcmx_ctx* ctx, int axis, double tau);
  * 1)^dim box around a tainted node) the results of every step and stage call
  * are unspecified and may be finite -- a NaN in a velocity is gone after one
  * step; an Inf survives and spreads one node per stage.  Outside that region
- * the results are the reference's.  No call reports a non-finite state: a
- * caller that must detect divergence scans a downloaded layer
- * (gcmx_download) for non-finite or implausibly large values. */
+ * the results are the reference's.  No step or stage call reports a non-finite
+ * state: a caller that must detect divergence calls gcmx_scan, which counts the
+ * non-finite values of the inner nodes and returns max |v| per component on the
+ * device (80 bytes come back, not a layer). */
 gcmx_status gcmx_step(gcmx_ctx* ctx, double tau);
 gcmx_status gcmx_set_kernel_path(gcmx_ctx* ctx, gcmx_path path);
 /* Step schedule of the fused path and the fused kernel's y rows per block
