@@ -92,39 +92,49 @@ __host__ __device__ constexpr int popc9(unsigned m) {
 	for (int i = 0; i < 9; i++) n += (m >> i) & 1u;
 	return n;
 }
-// u * v for a structural entry; exact w.r.t. the reference product fl(u * v).
-template <int SLOT, int SIGN>
-__device__ __forceinline__ double term(const IsoAxis& A, double v) {
-	double m;
-	if constexpr (SLOT == kOne) m = v;
-	else if constexpr (SLOT == kHalf) m = v * 0.5;
-	else if constexpr (SLOT == kA) m = A.a * v;
-	else if constexpr (SLOT == kB) m = A.b * v;
-	else if constexpr (SLOT == kG) m = A.g * v;
-	else if constexpr (SLOT == kP1) m = A.p1 * v;
-	else if constexpr (SLOT == kP2) m = A.p2 * v;
-	else m = A.s * v;
-	return SIGN > 0 ? m : -m;
-}
 
-// Unrolled sum over j of U(k, j) * V(j) (or U1(c, n) * r(n)) in ascending index
-// order, skipping structural zeros, starting from the first non-zero term.
-template <int S, bool ISU1, int ROW, int J = 0>
-struct RowSum {
-	template <class F>
-	__device__ __forceinline__ static double go(const IsoAxis& A, F val, double acc, bool first) {
-		if constexpr (J == 9) {
-			return acc;
-		} else {
-			constexpr Coef c = ISU1 ? iso_u1(S, ROW, J) : iso_u(S, ROW, J);
-			if constexpr (c.slot == kZero) {
-				return RowSum<S, ISU1, ROW, J + 1>::go(A, val, acc, first);
-			} else {
-				const double t = term<c.slot, c.sign>(A, val(J));
-				return RowSum<S, ISU1, ROW, J + 1>::go(A, val, first ? t : acc + t, false);
-			}
-		}
+// ------------------------------------------------------ stage templates --
+
+// The structure of a medium's stage: what RowSum ... node_update below need to
+// know.  Keyed by the axis struct the stage receives, so a call site names no
+// medium (pair_update<0, BS, KF0, P>(AX, ...)); TAG tells apart two media that
+// share an axis struct (the 2-D isotropic stage, kernels_2d.hip).  A Stage has
+//   M, NP               components; characteristic pairs (rows 2P, 2P+1 of U),
+//                       rows 2*NP .. M-1 read node values only
+//   u(S, k, j), u1(S, c, n)  the entries of U and U1
+//   term<SLOT, SIGN>(A, v)   u * v for a structural entry, exact w.r.t. the
+//                            reference product fl(u * v)
+//   coef<P>(A), wts<P>(A), kf<P>(A)   pair P's Newton data, Lagrange weights, floor(q)
+//   kFoot               the side of the foot row 2P reads (row 2P+1: the other)
+// and, for the one-plane kernel (plane_step.hpp), window(S), center_only(S),
+// pair_vel / pair_sig(S, P), kPlaneHet and plane_min_waves(bs, zt, het).
+template <class AX, class TAG = void>
+struct Stage;
+
+// What the isotropic stages (3-D here, 2-D in kernels_2d.hip) share: IsoAxis'
+// slots; row 2P has L > 0, its foot on the -S side; pair 0 moves at c1, the
+// others at c2.
+struct IsoStage {
+	static constexpr int kFoot = -1;
+	template <int SLOT, int SIGN>
+	__device__ __forceinline__ static double term(const IsoAxis& A, double v) {
+		double m;
+		if constexpr (SLOT == kOne) m = v;
+		else if constexpr (SLOT == kHalf) m = v * 0.5;
+		else if constexpr (SLOT == kA) m = A.a * v;
+		else if constexpr (SLOT == kB) m = A.b * v;
+		else if constexpr (SLOT == kG) m = A.g * v;
+		else if constexpr (SLOT == kP1) m = A.p1 * v;
+		else if constexpr (SLOT == kP2) m = A.p2 * v;
+		else m = A.s * v;
+		return SIGN > 0 ? m : -m;
 	}
+	template <int P>
+	__device__ __forceinline__ static const double* coef(const IsoAxis& A) { return (P == 0) ? A.c1 : A.c2; }
+	template <int P>
+	__device__ __forceinline__ static const double* wts(const IsoAxis& A) { return (P == 0) ? A.w1 : A.w2; }
+	template <int P>
+	__device__ __forceinline__ static int kf(const IsoAxis& A) { return (P == 0) ? A.kf1 : A.kf2; }
 };
 
 // Components of characteristic pair P (rows 2P, 2P+1 of U): the velocity
@@ -134,9 +144,46 @@ __host__ __device__ constexpr int pair_sig(int S, int P) {
 	return P == 0 ? sig3(S, S) : P == 1 ? sig3(tang1(S), S) : sig3(tang2(S), S);
 }
 
-// GCMX_FMA (the one-pass step's FMA build, kernels_xyz.hip compiled with
-// -DGCMX_FMA=1): with floor(q) = 0 and bs <= 2 a foot's interpolant is evaluated
-// in Lagrange form, w0 s0 + w1 s1 + w2 s2 with the host's weights
+template <>
+struct Stage<IsoAxis> : IsoStage {
+	static constexpr int M = 9, NP = 3;
+	__host__ __device__ static constexpr Coef u(int S, int k, int j) { return iso_u(S, k, j); }
+	__host__ __device__ static constexpr Coef u1(int S, int c, int n) { return iso_u1(S, c, n); }
+	__host__ __device__ static constexpr unsigned window(int S) { return iso_window(S); }
+	__host__ __device__ static constexpr unsigned center_only(int S) { return iso_center_only(S); }
+	__host__ __device__ static constexpr int pair_vel(int S, int P) { return gcmx::pair_vel(S, P); }
+	__host__ __device__ static constexpr int pair_sig(int S, int P) { return gcmx::pair_sig(S, P); }
+	// The one-plane step: no per-node materials (k_step_tx2 has them); 4 waves per
+	// SIMD (128 VGPRs), 2 at borderSize 3, whose windows spill 97 VGPRs to scratch
+	// at 4 (profiles/r6/bs3_resource_usage.txt).
+	static constexpr bool kPlaneHet = false;
+	__host__ __device__ static constexpr int plane_min_waves(int bs, int, bool) { return bs >= 3 ? 2 : 4; }
+};
+
+// Unrolled sum over j of U(k, j) * V(j) (or U1(c, n) * r(n)) in ascending index
+// order, skipping structural zeros, starting from the first non-zero term.
+template <int S, bool ISU1, int ROW, class TAG = void, int J = 0>
+struct RowSum {
+	template <class AX, class F>
+	__device__ __forceinline__ static double go(const AX& A, F val, double acc, bool first) {
+		using ST = Stage<AX, TAG>;
+		if constexpr (J == ST::M) {
+			return acc;
+		} else {
+			constexpr Coef c = ISU1 ? ST::u1(S, ROW, J) : ST::u(S, ROW, J);
+			if constexpr (c.slot == kZero) {
+				return RowSum<S, ISU1, ROW, TAG, J + 1>::go(A, val, acc, first);
+			} else {
+				const double t = ST::template term<c.slot, c.sign>(A, val(J));
+				return RowSum<S, ISU1, ROW, TAG, J + 1>::go(A, val, first ? t : acc + t, false);
+			}
+		}
+	}
+};
+
+// GCMX_FMA (the one-pass step's FMA build, kernels_xyz.hip / kernels_ortho.hip
+// compiled with -DGCMX_FMA=1): with floor(q) = 0 and bs <= 2 a foot's interpolant
+// is evaluated in Lagrange form, w0 s0 + w1 s1 + w2 s2 with the host's weights
 // (lagrange_weights), as one multiply and bs fused multiply-adds: the same
 // polynomial as minMaxInterpolate's Newton form (EqualDistanceLineInterpolator.hpp:56-71)
 // with other roundings, ~1e-16 relative, inside the north star's 1e-10 of the
@@ -153,14 +200,15 @@ __device__ __forceinline__ double lagrange_minmax(const double (&s)[BS + 1], con
 	return vlimit(ans, s[0], s[1]);
 }
 
-// Rows 2P (foot on the -S side, L > 0) and 2P+1 (+S side) of r = diag(U * V):
+// Rows 2P (foot on the kFoot side) and 2P+1 (the other side) of r = diag(U * V):
 // the two interpolations per component (minMaxInterpolate) and the U row sums.
 // W(j, o): component j at offset o along S (|o| <= BS).
-template <int S, int BS, bool KF0, int P, class WF>
-__device__ __forceinline__ void pair_update(const IsoAxis& A, WF W, double& ra, double& rb) {
-	const double* coef = (P == 0) ? A.c1 : A.c2;
-	const double* wts = (P == 0) ? A.w1 : A.w2;
-	const int kf = (P == 0) ? A.kf1 : A.kf2;
+template <int S, int BS, bool KF0, int P, class TAG = void, class AX, class WF>
+__device__ __forceinline__ void pair_update(const AX& A, WF W, double& ra, double& rb) {
+	using ST = Stage<AX, TAG>;
+	const double* coef = ST::template coef<P>(A);
+	const double* wts = ST::template wts<P>(A);
+	const int kf = ST::template kf<P>(A);
 	auto interp = [&](int j, int sh) {
 		double sv[BS + 1];
 #pragma unroll
@@ -168,43 +216,42 @@ __device__ __forceinline__ void pair_update(const IsoAxis& A, WF W, double& ra, 
 		if constexpr (GCMX_FMA && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
 		else return newton_minmax<BS, KF0>(sv, kf, coef);
 	};
-	ra = RowSum<S, false, 2 * P>::go(A, [&](int j) { return interp(j, -1); }, 0.0, true);
-	rb = RowSum<S, false, 2 * P + 1>::go(A, [&](int j) { return interp(j, 1); }, 0.0, true);
+	ra = RowSum<S, false, 2 * P, TAG>::go(A, [&](int j) { return interp(j, ST::kFoot); }, 0.0, true);
+	rb = RowSum<S, false, 2 * P + 1, TAG>::go(A, [&](int j) { return interp(j, -ST::kFoot); }, 0.0, true);
 }
 
-// Rows 6..8 (q == 0: the interpolant is the node value itself).  C(j): node value.
-template <int S, class CF>
-__device__ __forceinline__ void center_update(const IsoAxis& A, CF C, double (&r)[9]) {
-	r[6] = RowSum<S, false, 6>::go(A, C, 0.0, true);
-	r[7] = RowSum<S, false, 7>::go(A, C, 0.0, true);
-	r[8] = RowSum<S, false, 8>::go(A, C, 0.0, true);
+// dst[R] = the sum of row R, for R = R0 .. M-1, in that order.
+template <int S, bool ISU1, int R0, class TAG, class AX, class F, int M>
+__device__ __forceinline__ void row_sums(const AX& A, F val, double (&dst)[M]) {
+	static_assert(M == Stage<AX, TAG>::M, "one entry per row");
+	if constexpr (R0 < M) {
+		dst[R0] = RowSum<S, ISU1, R0, TAG>::go(A, val, 0.0, true);
+		row_sums<S, ISU1, R0 + 1, TAG>(A, val, dst);
+	}
+}
+
+// Rows 2*NP .. M-1 (q == 0: the interpolant is the node value itself).  C(j): node value.
+template <int S, class TAG = void, class AX, class CF, int M>
+__device__ __forceinline__ void center_update(const AX& A, CF C, double (&r)[M]) {
+	row_sums<S, false, 2 * Stage<AX, TAG>::NP, TAG>(A, C, r);
 }
 
 // out = U1 * r (localGcmStep's second product).
-template <int S>
-__device__ __forceinline__ void u1_apply(const IsoAxis& A, const double (&r)[9], double (&out)[9]) {
-	auto rv = [&](int n) { return r[n]; };
-	out[0] = RowSum<S, true, 0>::go(A, rv, 0.0, true);
-	out[1] = RowSum<S, true, 1>::go(A, rv, 0.0, true);
-	out[2] = RowSum<S, true, 2>::go(A, rv, 0.0, true);
-	out[3] = RowSum<S, true, 3>::go(A, rv, 0.0, true);
-	out[4] = RowSum<S, true, 4>::go(A, rv, 0.0, true);
-	out[5] = RowSum<S, true, 5>::go(A, rv, 0.0, true);
-	out[6] = RowSum<S, true, 6>::go(A, rv, 0.0, true);
-	out[7] = RowSum<S, true, 7>::go(A, rv, 0.0, true);
-	out[8] = RowSum<S, true, 8>::go(A, rv, 0.0, true);
+template <int S, class TAG = void, class AX, int M>
+__device__ __forceinline__ void u1_apply(const AX& A, const double (&r)[M], double (&out)[M]) {
+	row_sums<S, true, 0, TAG>(A, [&](int n) { return r[n]; }, out);
 }
 
 // One node's stage.  W(j, o): window component j at offset o along S
-// (|o| <= BS); C(j): node value of a component rows 6..8 read.
-template <int S, int BS, bool KF0, class WF, class CF>
-__device__ __forceinline__ void node_update(const IsoAxis& A, WF W, CF C, double (&out)[9]) {
-	double r[9];
-	pair_update<S, BS, KF0, 0>(A, W, r[0], r[1]);
-	pair_update<S, BS, KF0, 1>(A, W, r[2], r[3]);
-	pair_update<S, BS, KF0, 2>(A, W, r[4], r[5]);
-	center_update<S>(A, C, r);
-	u1_apply<S>(A, r, out);
+// (|o| <= BS); C(j): node value of a component the node-only rows read.
+template <int S, int BS, bool KF0, class TAG = void, class AX, class WF, class CF, int M>
+__device__ __forceinline__ void node_update(const AX& A, WF W, CF C, double (&out)[M]) {
+	double r[M];
+	pair_update<S, BS, KF0, 0, TAG>(A, W, r[0], r[1]);
+	pair_update<S, BS, KF0, 1, TAG>(A, W, r[2], r[3]);
+	if constexpr (Stage<AX, TAG>::NP > 2) pair_update<S, BS, KF0, 2, TAG>(A, W, r[4], r[5]);
+	center_update<S, TAG>(A, C, r);
+	u1_apply<S, TAG>(A, r, out);
 }
 
 // Per-component plane base pointers are uniform; per-thread offsets are 32-bit
@@ -224,22 +271,24 @@ __device__ __forceinline__ gptr sgpr_ptr(double* p) {
 	asm volatile("" : "+s"(q));
 	return q;
 }
-struct Planes {
-	gcptr b[kMaxM];
-	__device__ __forceinline__ Planes(const double* p, long long cs) {
+template <int N>  // N component planes (PlanesN<4>: the acoustic step's)
+struct PlanesN {
+	gcptr b[N];
+	__device__ __forceinline__ PlanesN(const double* p, long long cs) {
 #pragma unroll
-		for (int j = 0; j < kMaxM; j++) b[j] = sgpr_ptr(p + j * cs);
+		for (int j = 0; j < N; j++) b[j] = sgpr_ptr(p + j * cs);
 	}
 	__device__ __forceinline__ double ld(int j, unsigned off) const {
 		typedef const __attribute__((address_space(1))) char* gcb;
 		return *reinterpret_cast<gcptr>(reinterpret_cast<gcb>(b[j]) + (size_t)(off << 3));
 	}
 };
-struct PlanesW {
-	gptr b[kMaxM];
-	__device__ __forceinline__ PlanesW(double* p, long long cs) {
+template <int N>
+struct PlanesWN {
+	gptr b[N];
+	__device__ __forceinline__ PlanesWN(double* p, long long cs) {
 #pragma unroll
-		for (int j = 0; j < kMaxM; j++) b[j] = sgpr_ptr(p + j * cs);
+		for (int j = 0; j < N; j++) b[j] = sgpr_ptr(p + j * cs);
 	}
 	__device__ __forceinline__ void st(int j, unsigned off, double v) const {
 		typedef __attribute__((address_space(1))) char* gb;
@@ -250,6 +299,8 @@ struct PlanesW {
 		__builtin_nontemporal_store(v, reinterpret_cast<gptr>(reinterpret_cast<gb>(b[j]) + (size_t)(off << 3)));
 	}
 };
+using Planes = PlanesN<kMaxM>;
+using PlanesW = PlanesWN<kMaxM>;
 
 // Byte-offset form: the 32-bit per-lane offset is made opaque, so every access
 // is `global_load_dwordx2 v, v_off, s[base]` (SGPR base + 32-bit VGPR offset,

@@ -98,50 +98,16 @@ bool iso2_axis_extract(int S, const double* U, const double* U1, const double* L
 	return L[0] > 0 && L[1] == -L[0] && L[2] > 0 && L[3] == -L[2] && L[4] == 0.0;
 }
 
-// Unrolled sum over j of U(k, j) * V(j) (or U1(c, n) * r(n)) in ascending index
-// order, structural zeros skipped, from the first non-zero term (iso.hpp RowSum).
-template <int S, bool ISU1, int ROW, int J = 0>
-struct RowSum2 {
-	template <class F>
-	__device__ __forceinline__ static double go(const IsoAxis& A, F val, double acc, bool first) {
-		if constexpr (J == 5) {
-			return acc;
-		} else {
-			constexpr Coef c = ISU1 ? iso2_u1(S, ROW, J) : iso2_u(S, ROW, J);
-			if constexpr (c.slot == kZero) {
-				return RowSum2<S, ISU1, ROW, J + 1>::go(A, val, acc, first);
-			} else {
-				const double t = term<c.slot, c.sign>(A, val(J));
-				return RowSum2<S, ISU1, ROW, J + 1>::go(A, val, first ? t : acc + t, false);
-			}
-		}
-	}
+// The 2-D isotropic stage for iso.hpp's stage templates (node_update<S, BS, KF0,
+// Iso2D>): IsoAxis is the 3-D stage's axis struct too, hence the tag.  Two pairs;
+// row 4 reads the node.  (This file has the exact build only: Newton form.)
+struct Iso2D {};
+template <>
+struct Stage<IsoAxis, Iso2D> : IsoStage {
+	static constexpr int M = 5, NP = 2;
+	__host__ __device__ static constexpr Coef u(int S, int k, int j) { return iso2_u(S, k, j); }
+	__host__ __device__ static constexpr Coef u1(int S, int c, int n) { return iso2_u1(S, c, n); }
 };
-
-// One node's stage along S.  W(j, o): component j at offset o (|o| <= BS) for
-// the window components; C(j): the node value of a component row 4 reads.
-template <int S, int BS, bool KF0, class WF, class CF>
-__device__ __forceinline__ void node_update2(const IsoAxis& A, WF W, CF C, double (&out)[5]) {
-	double r[5];
-	auto interp = [&](int j, int sh, const double* coef, int kf) {
-		double sv[BS + 1];
-#pragma unroll
-		for (int i = 0; i <= BS; i++) sv[i] = W(j, sh * i);
-		return newton_minmax<BS, KF0>(sv, kf, coef);
-	};
-	// rows 2P: foot on the -S side (L > 0); rows 2P+1: the +S side
-	r[0] = RowSum2<S, false, 0>::go(A, [&](int j) { return interp(j, -1, A.c1, A.kf1); }, 0.0, true);
-	r[1] = RowSum2<S, false, 1>::go(A, [&](int j) { return interp(j, 1, A.c1, A.kf1); }, 0.0, true);
-	r[2] = RowSum2<S, false, 2>::go(A, [&](int j) { return interp(j, -1, A.c2, A.kf2); }, 0.0, true);
-	r[3] = RowSum2<S, false, 3>::go(A, [&](int j) { return interp(j, 1, A.c2, A.kf2); }, 0.0, true);
-	r[4] = RowSum2<S, false, 4>::go(A, C, 0.0, true);
-	auto rv = [&](int n) { return r[n]; };
-	out[0] = RowSum2<S, true, 0>::go(A, rv, 0.0, true);
-	out[1] = RowSum2<S, true, 1>::go(A, rv, 0.0, true);
-	out[2] = RowSum2<S, true, 2>::go(A, rv, 0.0, true);
-	out[3] = RowSum2<S, true, 3>::go(A, rv, 0.0, true);
-	out[4] = RowSum2<S, true, 4>::go(A, rv, 0.0, true);
-}
 
 // The one-pass 2-D step on the isotropic structure: the block / lane layout of
 // k_step2d below (T lanes along y, T - 2*BS of them written, the march along x
@@ -215,7 +181,7 @@ __global__ __launch_bounds__(T) void k_step2d_iso(const double* __restrict__ cur
 	for (int x = xb; x < xe; x++) {
 		load_ahead(x + PD, pw[PD - 1], pc[PD - 1]);
 		double xo[5];
-		node_update2<0, BS, KF0>(
+		node_update<0, BS, KF0, Iso2D>(
 		    AX, [&](int j, int o) { return win[wslot(WMX, j)][BS + o]; },
 		    [&](int j) { return ((WMX >> j) & 1u) ? win[wslot(WMX, j)][BS] : ctr[j]; }, xo);
 		double (*buf)[T] = lds[x & 1];
@@ -230,7 +196,7 @@ __global__ __launch_bounds__(T) void k_step2d_iso(const double* __restrict__ cur
 		__syncthreads();
 		if (out) {
 			double yo[5];
-			node_update2<1, BS, KF0>(
+			node_update<1, BS, KF0, Iso2D>(
 			    AY, [&](int j, int o) { return buf[wslot(WMY, j)][l + o]; },
 			    [&](int j) { return ((WMY >> j) & 1u) ? buf[wslot(WMY, j)][l] : xo[j]; }, yo);
 			const unsigned o = off + (unsigned)x * sx;

@@ -1,6 +1,6 @@
 // kernels_acoustic.hip -- the one-pass 3-D time step for acoustic media: X, Y
 // and Z stages of cubic::Engine::nextTimeStep (Engine.cpp:90-121) in one
-// kernel, in the block shape of k_step_ortho (kernels_ortho.hip).  Arithmetic
+// kernel, in the block shape of the one-plane kernel (plane_step.hpp).  Arithmetic
 // identical to k_stage_generic / the reference stage
 // (engine/cubic/GridCharacteristicMethod.hpp:42-52) through ac_pair (below).
 // One build, -ffp-contract=off: the reference's separate multiply and add
@@ -37,31 +37,6 @@ __device__ __forceinline__ void ac_pair(const AcAxis& A, VF V, PF P, double& v_o
 	v_out = r0 + r1;
 	p_out = A.p0 * r0 + A.p1 * r1;
 }
-
-// The four component planes of one layer at the block's x plane: SGPR bases,
-// 32-bit element offsets (iso.hpp's Planes, for M = 4).
-struct AcPlanes {
-	gcptr b[4];
-	__device__ __forceinline__ AcPlanes(const double* p, long long cs) {
-#pragma unroll
-		for (int j = 0; j < 4; j++) b[j] = sgpr_ptr(p + j * cs);
-	}
-	__device__ __forceinline__ double ld(int j, unsigned off) const {
-		typedef const __attribute__((address_space(1))) char* gcb;
-		return *reinterpret_cast<gcptr>(reinterpret_cast<gcb>(b[j]) + (size_t)(off << 3));
-	}
-};
-struct AcPlanesW {
-	gptr b[4];
-	__device__ __forceinline__ AcPlanesW(double* p, long long cs) {
-#pragma unroll
-		for (int j = 0; j < 4; j++) b[j] = sgpr_ptr(p + j * cs);
-	}
-	__device__ __forceinline__ void st_nt(int j, unsigned off, double v) const {
-		typedef __attribute__((address_space(1))) char* gb;
-		__builtin_nontemporal_store(v, reinterpret_cast<gptr>(reinterpret_cast<gb>(b[j]) + (size_t)(off << 3)));
-	}
-};
 
 // Minimum waves per SIMD of an instance (profiles/acoustic/resource_usage.txt):
 // the borderSize-1 instances fit 64 VGPRs (8 waves); within 64 the borderSize-2
@@ -116,8 +91,8 @@ __global__ __launch_bounds__(ZT, acoustic_min_waves(BS)) void k_step_acoustic(
 	const long long pbase = (long long)x * g.stride[0];
 	const unsigned plane = (unsigned)g.origin;  // node (x, 0, 0) from the bases
 	const unsigned base = plane + zc;
-	const AcPlanes src(in + pbase, g.cs);
-	const AcPlanesW out_p(outl + pbase, g.cs);
+	const PlanesN<4> src(in + pbase, g.cs);  // the four component planes
+	const PlanesWN<4> out_p(outl + pbase, g.cs);
 
 	if (z < 2 * BS) {  // ghost slots of both LDS row buffers: zero, never overwritten
 		const int gslot = (z < BS) ? z : (Z + z);
@@ -229,20 +204,10 @@ static const char* acoustic_name() {
 	return s.c_str();
 }
 
-// Rows per block, k_step_ortho's rule: 128 while the launch still has >= 1024
-// blocks; thinner launches halve it, down to 16 rows, to keep every CU busy.
-// Each block recomputes 2*BS X rows in its prologue.  `req` > 0 forces a value.
-static int acoustic_chunk_for(int Y, int nplanes, int req) {
-	int chunk = req > 0 ? req : 128;
-	if (req <= 0)
-		while (chunk > 16 && (long long)((Y + chunk - 1) / chunk) * nplanes < 1024) chunk /= 2;
-	return Y <= chunk ? Y : chunk;
-}
-
 template <int BS, int ZT>
 static void launch_acoustic_t(const double* in, double* out, const Geo& g, const AcAxis* a, int x0, int x1,
                               hipStream_t st, int req_chunk, const char** kname) {
-	const int chunk = acoustic_chunk_for(g.sizes[1], x1 - x0, req_chunk);
+	const int chunk = plane_chunk_for(g.sizes[1], x1 - x0, req_chunk);
 	const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * (x1 - x0));
 	if (a[0].kf == 0 && a[1].kf == 0 && a[2].kf == 0) {
 		hipLaunchKernelGGL((k_step_acoustic<BS, ZT, true>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1], a[2], x0,
@@ -258,12 +223,9 @@ static void launch_acoustic_t(const double* in, double* out, const Geo& g, const
 template <int BS>
 static void launch_acoustic_bs(const double* in, double* out, const Geo& g, const AcAxis* a, int x0, int x1,
                                hipStream_t st, int ch, const char** kn) {
-	const int Z = g.sizes[2];
-	if (Z <= 64) launch_acoustic_t<BS, 64>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 128) launch_acoustic_t<BS, 128>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 256) launch_acoustic_t<BS, 256>(in, out, g, a, x0, x1, st, ch, kn);
-	else if (Z <= 512) launch_acoustic_t<BS, 512>(in, out, g, a, x0, x1, st, ch, kn);
-	else launch_acoustic_t<BS, 1024>(in, out, g, a, x0, x1, st, ch, kn);
+	with_row_lanes(g.sizes[2], [&](auto ZC) {
+		launch_acoustic_t<BS, decltype(ZC)::value>(in, out, g, a, x0, x1, st, ch, kn);
+	});
 }
 
 bool acoustic_supported(const Geo& g) { return fused_supported(g) && g.M == 4; }

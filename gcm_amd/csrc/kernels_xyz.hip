@@ -1,5 +1,7 @@
-// kernels_xyz.hip -- the one-pass 3-D time step (X, Y and Z stages of
-// cubic::Engine::nextTimeStep, Engine.cpp:90-121, fused into one kernel).
+// kernels_xyz.hip -- the one-pass 3-D time step of the isotropic medium (X, Y
+// and Z stages of cubic::Engine::nextTimeStep, Engine.cpp:90-121, fused into one
+// kernel): k_step_tx2 with its z-seam kernel (below), the one-plane kernel
+// (plane_step.hpp) for what k_step_tx2 does not take, and their launcher.
 // Arithmetic identical to k_stage_generic / the reference stage
 // (engine/cubic/GridCharacteristicMethod.hpp:42-52) through node_update (iso.hpp).
 #include "iso.hpp"
@@ -8,7 +10,6 @@
 #include <string>
 #include <type_traits>
 
-namespace gcmx {
 // This file is compiled twice (Makefile): as the exact build (xyz_exact,
 // -ffp-contract=off: the reference's separate multiply and add roundings,
 // bitwise equal to the oracle) and as the FMA build (xyz_fma, -DGCMX_FMA=1
@@ -18,231 +19,20 @@ namespace gcmx {
 #define GCMX_FMA 0
 #endif
 #if GCMX_FMA
-#define GCMX_XYZ_NS xyz_fma
+#define GCMX_BUILD_NS xyz_fma
 #define GCMX_FP_TAG ", FMA"
 #else
-#define GCMX_XYZ_NS xyz_exact
+#define GCMX_BUILD_NS xyz_exact
 #define GCMX_FP_TAG ""
 #endif
-namespace GCMX_XYZ_NS {
+#include "plane_step.hpp"
 
-// ------------------------------------------------------------- fused xyz --
+namespace gcmx {
+namespace GCMX_BUILD_NS {
 
-// The whole time step in ONE pass (X stage, then Y, then Z, as
-// Engine::nextTimeStep orders them, Engine.cpp:90-121): block = one x plane, a
-// chunk of y rows and the whole z row.  Each thread marches y; at row y it
-//   * computes the X stage of row y+BS straight from the input layer (its
-//     2*BS+1 x-neighbours are plain loads; the neighbouring planes' blocks read
-//     the same lines, so they come from L2 / Infinity Cache, not HBM),
-//   * pushes that X result into a register window of 2*BS+1 rows and runs the
-//     Y stage of row y,
-//   * hands the Y result to the Z stage through double-buffered LDS.
-// HBM traffic: the input layer once, the output layer once (144 B/node/step).
-// Reads `in` (all components, x ghost planes valid), writes `outl`.
-//
-// Schedule (measured A/B on MI355X): the loop is rotated (Y, Z,
-// stores, then the X stage of the row that enters the window); the X stage
-// loads one characteristic pair (10 values) at a time with the next pair in
-// flight, which keeps the kernel at 128 VGPRs (two 512-thread blocks per CU);
-// the first pair of the next row is issued before this row's stores, so its
-// vmcnt wait never includes the stores (loads and stores retire in order on
-// gfx950); the output is written with non-temporal stores.
-// Precondition: every y/z ghost of both layers is zero, so the intermediate
-// results at ghost rows / columns are the constant 0.0.
-// k_step_tx2 (below) takes every launch with borderSize <= 2 and Z <= 512; this
-// kernel runs borderSize 3 and the rows of 513 .. 1024 the z split does not take.
-constexpr int kXyzMinWaves = 4;  // waves per SIMD (128 VGPRs)
-// borderSize 3 runs at 2 waves per SIMD (4 was the round-5 value): at 4 its
-// windows spill 97 VGPRs to scratch (profiles/r6/bs3_resource_usage.txt).
-constexpr int kXyzMinWavesBs3 = 2;
-constexpr int kXyzChunk = 128;  // rows per block (xyz_chunk_for)
-
-// UNI: the launch has Z == ZT (no idle lanes) and the three axes' tables are
-// identical (isotropic medium, equal h): one IsoAxis in scalar registers for all
-// three stages and no idle-lane selects.
-template <int BS, int ZT, bool KF0, bool UNI>
-__global__ __launch_bounds__(ZT, BS >= 3 ? kXyzMinWavesBs3 : kXyzMinWaves) void k_fused_xyz(
-    const double* __restrict__ in, double* __restrict__ outl, Geo g, IsoAxis AX, IsoAxis AY_,
-    IsoAxis AZ_, int x0, int chunk, int nplanes) {
-	const IsoAxis& AY = UNI ? AX : AY_;
-	const IsoAxis& AZ = UNI ? AX : AZ_;
-	constexpr unsigned WMX = iso_window(0);
-	constexpr unsigned CMX = iso_center_only(0);
-	constexpr unsigned WMY = iso_window(1);
-	constexpr unsigned CMY = iso_center_only(1);
-	constexpr int NWY = popc9(WMY);
-	constexpr int NCY = popc9(CMY);
-	constexpr unsigned WMZ = iso_window(2);
-	constexpr int NWZ = popc9(WMZ);
-	constexpr int W = 2 * BS + 1;
-	constexpr int LW = ZT + 2 * BS;
-	__shared__ double lds[2][NWZ][LW];
-
-	const int z = threadIdx.x;
-	const int Y = g.sizes[1], Z = g.sizes[2];
-	// 1-D grid of nchunks * nplanes blocks.  Blocks are dealt round-robin over
-	// the 8 XCDs (b % 8 share one, MI355X_MICROARCH.md §Workgroup dispatch): give
-	// each XCD a contiguous run of (chunk, plane) pairs in chunk-major order, so
-	// the 2*BS+1 x-neighbour planes a block re-reads were loaded by blocks of the
-	// same XCD, i.e. hit its L2.  Placement only; any mapping is correct.
-	int x, yb;
-	{
-		const int nx = (int)nplanes, T = (int)gridDim.x, b = (int)blockIdx.x;
-		const int p = xcd_order(b, T);
-		x = x0 + p % nx;
-		yb = (p / nx) * chunk;
-	}
-	const int ye = min(yb + chunk, Y);
-	const bool live = UNI || z < Z;
-	const int zc = live ? z : Z - 1;  // idle lanes shadow a valid column
-	const unsigned stx = (unsigned)g.stride[0];
-	const unsigned sty = (unsigned)g.stride[1];
-	// Plane bases in SGPRs at this block's plane x, element offsets relative to
-	// them: 32-bit offsets whatever the layer's size (onepass_layout_ok)
-	const long long pbase = (long long)x * g.stride[0];
-	const unsigned plane = (unsigned)g.origin;  // node (x, 0, 0) from the bases
-	const unsigned base = plane + zc;
-	const Planes src(in + pbase, g.cs);
-	const PlanesW out_p(outl + pbase, g.cs);
-
-	if (z < 2 * BS) {  // ghost slots of both LDS row buffers: zero, never overwritten
-		const int gslot = (z < BS) ? z : (Z + z);
-#pragma unroll
-		for (int q = 0; q < NWZ; q++) {
-			lds[0][q][gslot] = 0.0;
-			lds[1][q][gslot] = 0.0;
-		}
-	}
-
-	// X stage of row r, loaded one characteristic pair (10 values) at a time with
-	// the next pair in flight: at most two pairs are live in registers.
-	typedef double PairWin[2][W];
-	auto pair_load = [&](auto PC, PairWin& w, unsigned o) {
-		constexpr int P = decltype(PC)::value;
-#pragma unroll
-		for (int k = 0; k < W; k++) {
-			w[0][k] = src.ld(pair_vel(0, P), o + (unsigned)(k - BS) * stx);
-			w[1][k] = src.ld(pair_sig(0, P), o + (unsigned)(k - BS) * stx);
-		}
-	};
-	auto pair_acc = [&](auto PC, const PairWin& w) {
-		constexpr int P = decltype(PC)::value;
-		return [&w](int j, int o) { return j == pair_vel(0, P) ? w[0][BS + o] : w[1][BS + o]; };
-	};
-	auto sched_fence = [] { __builtin_amdgcn_sched_barrier(0); };
-	using P0 = std::integral_constant<int, 0>;
-	using P1 = std::integral_constant<int, 1>;
-	using P2 = std::integral_constant<int, 2>;
-	// wa holds pair 0 of row r (already issued); loads pairs 1, 2 and the
-	// node-only components as it goes.
-	auto x_stage_rest = [&](PairWin& wa, int r, double (&xr)[9]) {
-		const unsigned o = base + (unsigned)r * sty;
-		PairWin wb;
-		pair_load(P1{}, wb, o);
-		double rr[9], n0[9], cv[9];
-		pair_update<0, BS, KF0, 0>(AX, pair_acc(P0{}, wa), rr[0], rr[1]);
-		n0[pair_vel(0, 0)] = wa[0][BS];
-		n0[pair_sig(0, 0)] = wa[1][BS];
-		sched_fence();
-		pair_load(P2{}, wa, o);
-		pair_update<0, BS, KF0, 1>(AX, pair_acc(P1{}, wb), rr[2], rr[3]);
-		n0[pair_vel(0, 1)] = wb[0][BS];
-		n0[pair_sig(0, 1)] = wb[1][BS];
-		sched_fence();
-#pragma unroll
-		for (int j = 0; j < 9; j++)
-			if ((CMX >> j) & 1u) cv[j] = src.ld(j, o);
-		pair_update<0, BS, KF0, 2>(AX, pair_acc(P2{}, wa), rr[4], rr[5]);
-		n0[pair_vel(0, 2)] = wa[0][BS];
-		n0[pair_sig(0, 2)] = wa[1][BS];
-		sched_fence();
-		center_update<0>(AX, [&](int j) { return ((WMX >> j) & 1u) ? n0[j] : cv[j]; }, rr);
-		u1_apply<0>(AX, rr, xr);
-	};
-	auto x_load_a = [&](PairWin& wa, int r) { pair_load(P0{}, wa, base + (unsigned)r * sty); };
-
-	// Y window over X results of rows y-BS..y+BS; node-only components of rows
-	// y..y+BS wait in a small delay line.
-	double win[NWY][W];
-	double cen[BS + 1][NCY > 0 ? NCY : 1];
-	auto push = [&](const double (&xr)[9], int slot) {  // slot: window index of the row
-#pragma unroll
-		for (int j = 0; j < 9; j++) {
-			if ((WMY >> j) & 1u) win[wslot(WMY, j)][slot] = xr[j];
-			if ((CMY >> j) & 1u) {
-				if (slot >= BS) cen[slot - BS][wslot(CMY, j)] = xr[j];
-			}
-		}
-	};
-	// Rotated schedule: the loads of an X row are issued at the END of an
-	// iteration and consumed after the next iteration's stores, so in every path
-	// into the loop they are older than 9 stores and the compiler's vmcnt waits
-	// never include the stores' completion.  Stores, LDS writes and the Z stage
-	// are unconditional (idle lanes z >= Z write 0.0 into the first z ghost, which
-	// the precondition keeps zero), and the in-loop X rows are loaded without a
-	// branch: rows outside [0, Y) are zero ghost rows, clamped into the plane.
-	// prologue: X results of rows yb-BS .. yb+BS
-#pragma unroll
-	for (int k = 0; k < W; k++) {
-		const int r = yb - BS + k;
-		double xr[9];
-		if (r >= 0 && r < Y) {
-			PairWin wa;
-			x_load_a(wa, r);
-			x_stage_rest(wa, r, xr);
-		} else {
-#pragma unroll
-			for (int j = 0; j < 9; j++) xr[j] = 0.0;
-		}
-		push(xr, k);
-	}
-	auto clamp_row = [&](int r) { return r < Y + BS - 1 ? r : Y + BS - 1; };
-	const unsigned zo = live ? (unsigned)z : (unsigned)Z;
-
-	int buf = 0;
-#pragma unroll 1
-	for (int y = yb; y < ye; y++) {
-		double yv[9];
-		node_update<1, BS, KF0>(
-		    AY, [&](int j, int o) { return win[wslot(WMY, j)][BS + o]; },
-		    [&](int j) { return ((WMY >> j) & 1u) ? win[wslot(WMY, j)][BS] : cen[0][wslot(CMY, j)]; },
-		    yv);
-#pragma unroll
-		for (int j = 0; j < 9; j++)
-			if ((WMZ >> j) & 1u) lds[buf][wslot(WMZ, j)][BS + z] = live ? yv[j] : 0.0;
-		PairWin wa_next;
-		__syncthreads();
-		{
-			double zv[9];
-			node_update<2, BS, KF0>(
-			    AZ, [&](int j, int o) { return lds[buf][wslot(WMZ, j)][BS + z + o]; },
-			    [&](int j) { return ((WMZ >> j) & 1u) ? lds[buf][wslot(WMZ, j)][BS + z] : yv[j]; }, zv);
-			const unsigned offo = plane + (unsigned)y * sty + zo;
-			// next row's first pair: loads older than this row's stores
-			sched_fence();
-			x_load_a(wa_next, clamp_row(y + BS + 1));
-			sched_fence();
-#pragma unroll
-			for (int c = 0; c < 9; c++) out_p.st_nt(c, offo, live ? zv[c] : 0.0);
-		}
-		buf ^= 1;
-#pragma unroll
-		for (int q = 0; q < NWY; q++)
-#pragma unroll
-			for (int o = 0; o < W - 1; o++) win[q][o] = win[q][o + 1];
-#pragma unroll
-		for (int k = 0; k < BS; k++)
-#pragma unroll
-			for (int q = 0; q < (NCY > 0 ? NCY : 1); q++) cen[k][q] = cen[k + 1][q];
-		{  // X stage of row y+BS+1 (zero ghost rows give zero) -> window slot W-1
-			double xr[9];
-			sched_fence();
-			x_stage_rest(wa_next, clamp_row(y + BS + 1), xr);
-			push(xr, W - 1);
-			sched_fence();
-		}
-	}
-}
+// k_step_tx2 (below) takes every launch with borderSize <= 2 and Z <= 512; the
+// one-plane kernel (reported as k_fused_xyz) runs borderSize 3 and the rows of
+// 513 .. 1024 the z split does not take.
 
 // ------------------------------------------------ two planes per thread --
 
@@ -1346,18 +1136,6 @@ static int device_cus() {
 	return n;
 }
 
-// Rows per block (k_fused_xyz): kXyzChunk (128) while the launch still has >= 1024 blocks
-// (two rounds of the 512 resident blocks, 2 per CU); thinner slabs (multi-GPU
-// X slabs, the boundary planes) halve it, down to 16 rows, to keep every CU
-// busy.  Each block recomputes 2*BS X rows in its prologue, so a chunk of c
-// rows costs (c + 2*BS) / c of the X stage.  `req` > 0 forces a value.
-static int xyz_chunk_for(int Y, int nplanes, int req, int start = kXyzChunk, int min_blocks = 1024) {
-	int chunk = req > 0 ? req : start;
-	if (req <= 0)
-		while (chunk > 16 && (long long)((Y + chunk - 1) / chunk) * nplanes < min_blocks) chunk /= 2;
-	return Y <= chunk ? Y : chunk;
-}
-
 // z split (k_step_tx2<BS, P, ..., ZS> + k_zseam): parts of P lanes, uniform
 // medium (equal axes, floor(q) = 0); FACES: the y/z face conditions.
 template <int BS, int P, bool FACES>
@@ -1451,33 +1229,26 @@ static void launch_xyz_t(const double* in, double* out, const Geo& g, const IsoA
 		x0 = xb0;
 		x1 = xb1;
 	}
-	const int chunk = xyz_chunk_for(g.sizes[1], x1 - x0, req_chunk);
+	const int chunk = plane_chunk_for(g.sizes[1], x1 - x0, req_chunk);
 	const dim3 grid(((g.sizes[1] + chunk - 1) / chunk) * (x1 - x0));
-	if (uni) {
-		hipLaunchKernelGGL((k_fused_xyz<BS, ZT, true, true>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1],
-		                   a[2], x0, chunk, x1 - x0);
-		*kname = xyz_name<BS, ZT, true, true>();
-	} else if (kf0) {
-		hipLaunchKernelGGL((k_fused_xyz<BS, ZT, true, false>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1],
-		                   a[2], x0, chunk, x1 - x0);
-		*kname = xyz_name<BS, ZT, true, false>();
-	} else {
-		hipLaunchKernelGGL((k_fused_xyz<BS, ZT, false, false>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1],
-		                   a[2], x0, chunk, x1 - x0);
-		*kname = xyz_name<BS, ZT, false, false>();
-	}
+	auto go1 = [&](auto KC, auto UC) {
+		constexpr bool K = decltype(KC)::value, U = decltype(UC)::value;
+		hipLaunchKernelGGL((k_step_plane<IsoAxis, BS, ZT, K, U, false>), grid, dim3(ZT), 0, st, in, out, g, a[0], a[1],
+		                   a[2], x0, chunk, x1 - x0, PlaneHet<IsoAxis>{});
+		*kname = xyz_name<BS, ZT, K, U>();
+	};
+	if (uni) go1(std::true_type{}, std::true_type{});
+	else if (kf0) go1(std::true_type{}, std::false_type{});
+	else go1(std::false_type{}, std::false_type{});
 }
 
 template <int BS>
 static bool launch_xyz_bs(const double* in, double* out, const Geo& g, const IsoAxis* a, int x0,
                           int x1, int xb0, int xb1, hipStream_t st, int ch, const FaceBC* fb,
                           const char** kn, const HetMaterials* het) {
-	const int Z = g.sizes[2];
-	if (Z <= 64) launch_xyz_t<BS, 64>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
-	else if (Z <= 128) launch_xyz_t<BS, 128>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
-	else if (Z <= 256) launch_xyz_t<BS, 256>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
-	else if (Z <= 512) launch_xyz_t<BS, 512>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
-	else launch_xyz_t<BS, 1024>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
+	with_row_lanes(g.sizes[2], [&](auto ZC) {
+		launch_xyz_t<BS, decltype(ZC)::value>(in, out, g, a, x0, x1, xb0, xb1, st, ch, fb, kn, het);
+	});
 	return true;
 }
 
@@ -1531,7 +1302,7 @@ bool launch_fused_xyz(const double* in, double* out, const Geo& g, const IsoAxis
 	}
 }
 
-}  // namespace GCMX_XYZ_NS
+}  // namespace GCMX_BUILD_NS
 
 #if !GCMX_FMA
 // CUs the one-pass step leaves free while it covers planes [x0, x1) in one
@@ -1540,10 +1311,10 @@ bool launch_fused_xyz(const double* in, double* out, const Geo& g, const IsoAxis
 int step_free_cus(const Geo& g, int x0, int x1, int req_chunk, int cus_in) {
 	const int Z = g.sizes[2];
 	if (!fused_supported(g) || g.bs > 2 || Z > 512 || x1 <= x0) return -1;
-	const int ZT = Z <= 64 ? 64 : Z <= 128 ? 128 : Z <= 256 ? 256 : 512;
-	const int per_cu = 512 / ZT, cus = cus_in > 0 ? cus_in : GCMX_XYZ_NS::device_cus();
+	const int ZT = row_lanes(Z);
+	const int per_cu = 512 / ZT, cus = cus_in > 0 ? cus_in : GCMX_BUILD_NS::device_cus();
 	const int npair = (x1 - x0 + ((g.gx0 + x0) & 1) + 1) / 2;
-	const int chunk = GCMX_XYZ_NS::tx2_chunk_for(g.sizes[1], npair, req_chunk, cus * per_cu);
+	const int chunk = GCMX_BUILD_NS::tx2_chunk_for(g.sizes[1], npair, req_chunk, cus * per_cu);
 	const long long blocks = (long long)((g.sizes[1] + chunk - 1) / chunk) * npair;
 	const long long slots = (long long)cus * per_cu;
 	return blocks >= slots ? 0 : (int)((slots - blocks) / per_cu);
@@ -1576,7 +1347,7 @@ bool zs_admissible(const Geo& g, const IsoAxis* a) {
 	if (zs_part(g) <= 0) return false;
 	for (int s = 0; s < 3; s++)
 		if (a[s].kf1 != 0 || a[s].kf2 != 0) return false;
-	return GCMX_XYZ_NS::same_axis(a[0], a[1]) && GCMX_XYZ_NS::same_axis(a[0], a[2]);
+	return GCMX_BUILD_NS::same_axis(a[0], a[1]) && GCMX_BUILD_NS::same_axis(a[0], a[2]);
 }
 
 #endif

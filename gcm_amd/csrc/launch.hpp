@@ -4,6 +4,7 @@
 #include "common.hpp"
 
 #include <string>
+#include <type_traits>
 
 namespace gcmx {
 
@@ -107,6 +108,42 @@ bool launch_line_z(const double* cur, double* nxt, const Geo& g, const IsoAxis& 
                    int x1, hipStream_t st);
 // The one-pass step needs 2*bs <= Z <= 1024 (one block spans a whole z row).
 bool fused_supported(const Geo& g);
+// The block width of a z row in the one-pass kernels (their ZT): the smallest of
+// 64 .. 1024 lanes that holds it; f(std::integral_constant<int, ZT>) for it.
+constexpr int row_lanes(int Z) { return Z <= 64 ? 64 : Z <= 128 ? 128 : Z <= 256 ? 256 : Z <= 512 ? 512 : 1024; }
+template <class F>
+inline void with_row_lanes(int Z, F f) {
+	switch (row_lanes(Z)) {
+	case 64: f(std::integral_constant<int, 64>{}); break;
+	case 128: f(std::integral_constant<int, 128>{}); break;
+	case 256: f(std::integral_constant<int, 256>{}); break;
+	case 512: f(std::integral_constant<int, 512>{}); break;
+	default: f(std::integral_constant<int, 1024>{}); break;
+	}
+}
+// Rows per block of the one-plane kernels (block = one x plane, a chunk of y
+// rows, the whole z row: plane_step.hpp, k_step_acoustic): `start` (128) while
+// the launch still has >= min_blocks (1024) blocks, i.e. two rounds of the 512
+// resident blocks at 2 per CU; thinner launches (multi-GPU X slabs, the boundary
+// planes) halve it, down to 16 rows, to keep every CU busy.  Each block
+// recomputes 2*BS X rows in its prologue, so a chunk of c rows costs
+// (c + 2*BS) / c of the X stage.  `req` > 0 forces a value.
+inline int plane_chunk_for(int Y, int nplanes, int req, int start = 128, int min_blocks = 1024) {
+	int chunk = req > 0 ? req : start;
+	if (req <= 0)
+		while (chunk > 16 && (long long)((Y + chunk - 1) / chunk) * nplanes < min_blocks) chunk /= 2;
+	return Y <= chunk ? Y : chunk;
+}
+// Per-node materials of the one-plane step (plane_step.hpp's HET instances):
+// the materials' axis tables and the device ids of the inner nodes in linear
+// [x][y][z] order (gcmx_set_material_ids' layout).
+template <class AX>
+struct PlaneHet {
+	const AX* tab;
+	const uint8_t* ids;
+	int n;
+	int pad_;
+};
 // One cubic border condition as the one-pass step applies it to a ghost: the
 // components in `mask` set to -inner + two_v[c], the others mirrored
 // (BorderConditions.hpp:94-114; two_v = 2 * timeDependency(t)).
@@ -154,7 +191,7 @@ void launch_set_face_tables(BorderQ* bq_d, FaceCond* fc_d, const FaceTables& t, 
 // on == 0 carries only the ODE factor.
 bool fused_faces_supported(const Geo& g);
 // One pass per time step: X, Y, Z stages of planes [x0, x1), `a` = the three axes.
-// `chunk`: y rows per block (0 = automatic, kernels_xyz.hip: xyz_chunk_for).
+// `chunk`: y rows per block (0 = automatic: tx2_chunk_for, kernels_xyz.hip, or plane_chunk_for).
 // `faces`: y/z face conditions and the ODE factor (null, or on == 0: y/z ghosts of
 // both layers are zero); the ODE factor needs the k_step_tx2 path (bs <= 2, Z <= 512).
 // Per-node materials for the one-pass step (k_step_tx2<..., HET>): per material

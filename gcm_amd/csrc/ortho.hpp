@@ -41,17 +41,12 @@ bool ortho_axis_extract(int s, const double* U, const double* U1, const double* 
 // rows per block (0 = automatic).  Needs ortho_supported(g), y/z ghosts of both
 // layers zero, x ghost planes of `in` valid.  Two builds, as kernels_xyz.hip's.
 bool ortho_supported(const Geo& g);  // fused_supported(g), and Z <= 512 at borderSize 3
-// Per-node materials for the step (k_step_ortho<..., HET>): per material three
+// Per-node materials for the step (the HET instances): per material three
 // OrthoAxis (x, y, z; every pair with floor(q) = 0, its feet on the sides the
 // kernel reads), at most kHetMaxMaterials of them, and the device ids of the
 // inner nodes in linear [x][y][z] order (gcmx_set_material_ids' layout).  Then
 // `a` is unused and may be null.
-struct OrthoHet {
-	const OrthoAxis* tab;  // [n][3], device
-	const uint8_t* ids;
-	int n;
-	int pad_;
-};
+using OrthoHet = PlaneHet<OrthoAxis>;  // tab: [n][3], device
 // The HET instances: borderSize 1..3 with rows up to 512 nodes, borderSize 1
 // also up to 1024.  A 1024-thread block leaves 128 VGPRs, within which the
 // per-lane coefficients do not fit beside the borderSize-2 windows (the instance
@@ -121,103 +116,50 @@ __host__ __device__ constexpr Coef ortho_u1(int S, int c, int n) {
 	return cz();
 }
 
-// Components read at the neighbours (rows 0..5) / only at the node (rows 6..8).
-__host__ __device__ constexpr unsigned ortho_window(int S) {
-	unsigned m = 0;
-	for (int p = 0; p < 3; p++) m |= bit(opair_vel(S, p)) | bit(opair_sig(S, p));
-	return m;
-}
-__host__ __device__ constexpr unsigned ortho_center_only(int S) {
-	return bit(ozero_comp(S, 0)) | bit(ozero_comp(S, 1)) | bit(ozero_comp(S, 2));
-}
-static_assert(ortho_window(0) == iso_window(0) && ortho_window(1) == iso_window(1) &&
-                  ortho_window(2) == iso_window(2),
-              "the orthotropic stages read the isotropic window components");
-
-// u * v for a structural entry; exact w.r.t. the reference product fl(u * v).
-template <int SLOT, int SIGN>
-__device__ __forceinline__ double oterm(const OrthoAxis& A, double v) {
-	double m;
-	if constexpr (SLOT == kOne) m = v;
-	else if constexpr (SLOT == kHalf) m = v * 0.5;
-	else if constexpr (SLOT >= kOE) m = A.e[SLOT - kOE] * v;
-	else if constexpr (SLOT >= kOP) m = A.p[SLOT - kOP] * v;
-	else if constexpr (SLOT >= kOG) m = A.g[SLOT - kOG] * v;
-	else m = A.a[SLOT - kOA] * v;
-	return SIGN > 0 ? m : -m;
-}
-
-// Unrolled sum over j of U(k, j) * V(j) (or U1(c, n) * r(n)) in ascending index
-// order, skipping structural zeros, starting from the first non-zero term.
-template <int S, bool ISU1, int ROW, int J = 0>
-struct ORowSum {
-	template <class F>
-	__device__ __forceinline__ static double go(const OrthoAxis& A, F val, double acc, bool first) {
-		if constexpr (J == 9) {
-			return acc;
-		} else {
-			constexpr Coef c = ISU1 ? ortho_u1(S, ROW, J) : ortho_u(S, ROW, J);
-			if constexpr (c.slot == kZero) {
-				return ORowSum<S, ISU1, ROW, J + 1>::go(A, val, acc, first);
-			} else {
-				const double t = oterm<c.slot, c.sign>(A, val(J));
-				return ORowSum<S, ISU1, ROW, J + 1>::go(A, val, first ? t : acc + t, false);
-			}
-		}
+// The orthotropic stage for iso.hpp's stage templates: row 2P has L < 0, its
+// foot on the +S side; every pair has its own speed.
+template <>
+struct Stage<OrthoAxis> {
+	static constexpr int M = 9, NP = 3, kFoot = 1;
+	__host__ __device__ static constexpr Coef u(int S, int k, int j) { return ortho_u(S, k, j); }
+	__host__ __device__ static constexpr Coef u1(int S, int c, int n) { return ortho_u1(S, c, n); }
+	// Components read at the neighbours (rows 0..5) / only at the node (rows 6..8).
+	__host__ __device__ static constexpr unsigned window(int S) {
+		unsigned m = 0;
+		for (int p = 0; p < 3; p++) m |= bit(opair_vel(S, p)) | bit(opair_sig(S, p));
+		return m;
+	}
+	__host__ __device__ static constexpr unsigned center_only(int S) {
+		return bit(ozero_comp(S, 0)) | bit(ozero_comp(S, 1)) | bit(ozero_comp(S, 2));
+	}
+	__host__ __device__ static constexpr int pair_vel(int S, int P) { return opair_vel(S, P); }
+	__host__ __device__ static constexpr int pair_sig(int S, int P) { return opair_sig(S, P); }
+	// u * v for a structural entry; exact w.r.t. the reference product fl(u * v).
+	template <int SLOT, int SIGN>
+	__device__ __forceinline__ static double term(const OrthoAxis& A, double v) {
+		double m;
+		if constexpr (SLOT == kOne) m = v;
+		else if constexpr (SLOT == kHalf) m = v * 0.5;
+		else if constexpr (SLOT >= kOE) m = A.e[SLOT - kOE] * v;
+		else if constexpr (SLOT >= kOP) m = A.p[SLOT - kOP] * v;
+		else if constexpr (SLOT >= kOG) m = A.g[SLOT - kOG] * v;
+		else m = A.a[SLOT - kOA] * v;
+		return SIGN > 0 ? m : -m;
+	}
+	template <int P>
+	__device__ __forceinline__ static const double* coef(const OrthoAxis& A) { return A.c[P]; }
+	template <int P>
+	__device__ __forceinline__ static const double* wts(const OrthoAxis& A) { return A.w[P]; }
+	template <int P>
+	__device__ __forceinline__ static int kf(const OrthoAxis& A) { return A.kf[P]; }
+	// The one-plane step (plane_step.hpp): per-node materials are built; waves per SIMD.
+	static constexpr bool kPlaneHet = true;
+	__host__ __device__ static constexpr int plane_min_waves(int bs, int zt, bool het) {
+		return ortho_min_waves(bs, zt, het);
 	}
 };
-
-// Rows 2P (L < 0: foot on the +S side) and 2P+1 (-S side) of r = diag(U * V).
-// W(j, o): component j at offset o along S (|o| <= BS).
-template <int S, int BS, bool KF0, int P, class WF>
-__device__ __forceinline__ void opair_update(const OrthoAxis& A, WF W, double& ra, double& rb) {
-	const double* coef = A.c[P];
-	const double* wts = A.w[P];
-	const int kf = A.kf[P];
-	auto interp = [&](int j, int sh) {
-		double sv[BS + 1];
-#pragma unroll
-		for (int i = 0; i <= BS; i++) sv[i] = W(j, sh * i);
-		if constexpr (GCMX_FMA && KF0 && BS <= 2) return lagrange_minmax<BS>(sv, wts);
-		else return newton_minmax<BS, KF0>(sv, kf, coef);
-	};
-	ra = ORowSum<S, false, 2 * P>::go(A, [&](int j) { return interp(j, 1); }, 0.0, true);
-	rb = ORowSum<S, false, 2 * P + 1>::go(A, [&](int j) { return interp(j, -1); }, 0.0, true);
-}
-
-// Rows 6..8 (q == 0: the interpolant is the node value itself).  C(j): node value.
-template <int S, class CF>
-__device__ __forceinline__ void ocenter_update(const OrthoAxis& A, CF C, double (&r)[9]) {
-	r[6] = ORowSum<S, false, 6>::go(A, C, 0.0, true);
-	r[7] = ORowSum<S, false, 7>::go(A, C, 0.0, true);
-	r[8] = ORowSum<S, false, 8>::go(A, C, 0.0, true);
-}
-
-// out = U1 * r (localGcmStep's second product).
-template <int S>
-__device__ __forceinline__ void ou1_apply(const OrthoAxis& A, const double (&r)[9], double (&out)[9]) {
-	auto rv = [&](int n) { return r[n]; };
-	out[0] = ORowSum<S, true, 0>::go(A, rv, 0.0, true);
-	out[1] = ORowSum<S, true, 1>::go(A, rv, 0.0, true);
-	out[2] = ORowSum<S, true, 2>::go(A, rv, 0.0, true);
-	out[3] = ORowSum<S, true, 3>::go(A, rv, 0.0, true);
-	out[4] = ORowSum<S, true, 4>::go(A, rv, 0.0, true);
-	out[5] = ORowSum<S, true, 5>::go(A, rv, 0.0, true);
-	out[6] = ORowSum<S, true, 6>::go(A, rv, 0.0, true);
-	out[7] = ORowSum<S, true, 7>::go(A, rv, 0.0, true);
-	out[8] = ORowSum<S, true, 8>::go(A, rv, 0.0, true);
-}
-
-// One node's stage.  W(j, o): window component j at offset o along S
-// (|o| <= BS); C(j): node value of a component rows 6..8 read.
-template <int S, int BS, bool KF0, class WF, class CF>
-__device__ __forceinline__ void onode_update(const OrthoAxis& A, WF W, CF C, double (&out)[9]) {
-	double r[9];
-	opair_update<S, BS, KF0, 0>(A, W, r[0], r[1]);
-	opair_update<S, BS, KF0, 1>(A, W, r[2], r[3]);
-	opair_update<S, BS, KF0, 2>(A, W, r[4], r[5]);
-	ocenter_update<S>(A, C, r);
-	ou1_apply<S>(A, r, out);
-}
+static_assert(Stage<OrthoAxis>::window(0) == iso_window(0) && Stage<OrthoAxis>::window(1) == iso_window(1) &&
+                  Stage<OrthoAxis>::window(2) == iso_window(2),
+              "the orthotropic stages read the isotropic window components");
 
 }  // namespace gcmx

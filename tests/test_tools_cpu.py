@@ -24,6 +24,15 @@ def test_readable_matches_the_library_symbols():
     assert r("void gcmx::xyz_fma::k_step_tx2<2, 64, true, true, true, true, false>(x)") == \
         "k_step_tx2<2, 64, KF0, UNI, FACES, HET, FMA>"
     assert r("void gcmx::xyz_fma::k_fused_xyz<3, 1024, true, true>(x)") == "k_fused_xyz<3, 1024, KF0, UNI, FMA>"
+    # the one-plane kernel shared by the media keeps its medium's reported name
+    assert r("void gcmx::xyz_fma::k_step_plane<gcmx::IsoAxis, 3, 1024, true, true, false>(x)") == \
+        "k_fused_xyz<3, 1024, KF0, UNI, FMA>"
+    assert r("void gcmx::xyz_exact::k_step_plane<gcmx::IsoAxis, 3, 64, false, false, false>(x)") == \
+        "k_fused_xyz<3, 64, !KF0, !UNI>"
+    assert r("void gcmx::ortho_fma::k_step_plane<gcmx::OrthoAxis, 2, 256, true, false, true>(x)") == \
+        "k_step_ortho<2, 256, KF0, HET, FMA>"
+    assert r("void gcmx::ortho_exact::k_step_plane<gcmx::OrthoAxis, 1, 1024, false, false, false>(x)") == \
+        "k_step_ortho<1, 1024, !KF0>"
 
 
 def test_the_committed_pmc_records_name_their_grid_and_instance():

@@ -19,22 +19,30 @@ def agg(path, counter):
 
 def readable(rocprof_name):
     """'void gcmx::k_step_tx2<2, 512, true, true, false>(...)' -> the library's
-    symbol form 'k_step_tx2<2, 512, KF0, UNI, !FACES>' (gcmx_profile_kernel)."""
+    symbol form 'k_step_tx2<2, 512, KF0, UNI, !FACES>' (gcmx_profile_kernel).
+    The one-plane kernel k_step_plane<medium, BS, ZT, KF0, UNI, HET> goes by its
+    medium's name there: k_fused_xyz<BS, ZT, KF0, UNI> (isotropic) or
+    k_step_ortho<BS, ZT, KF0[, HET]> (orthotropic)."""
     import re
-    m = re.search(r"(k_step_tx2|k_fused_xyz)<([^>]*)>", rocprof_name)
+    m = re.search(r"(k_step_tx2|k_fused_xyz|k_step_plane)<([^>]*)>", rocprof_name)
     if not m:
         return rocprof_name
-    a = [x.strip() for x in m.group(2).split(",")]
+    name, a = m.group(1), [x.strip() for x in m.group(2).split(",")]
+    if name == "k_step_plane":
+        name = "k_step_ortho" if "Ortho" in a[0] else "k_fused_xyz"
+        a = a[1:5] if name == "k_fused_xyz" else a[1:4] + ["false", "false"] + a[5:6]
     flags = ["KF0", "UNI", "FACES"]
     out = a[:2] + [(f if v == "true" else "!" + f) for f, v in zip(flags, a[2:5])]
-    # k_step_tx2's HET and ZS flags appear in the library's name only when set
+    if name == "k_step_ortho":  # no UNI / FACES flags in its name
+        out = out[:3]
+    # the HET and ZS flags appear in the library's name only when set
     out += [f for f, v in zip(["HET", "ZS"], a[5:7]) if v == "true"]
     # a UNI instance launched on the 8-byte path (8th flag false) is named ", N8"
-    if m.group(1) == "k_step_tx2" and a[3] == "true" and a[7:8] == ["false"]:
+    if name == "k_step_tx2" and a[3] == "true" and a[7:8] == ["false"]:
         out.append("N8")
-    if "xyz_fma::" in rocprof_name:  # the contracted build (gcmx_set_fp_mode), as the library names it
+    if "_fma::" in rocprof_name:  # the contracted build (gcmx_set_fp_mode), as the library names it
         out.append("FMA")
-    return f"{m.group(1)}<{', '.join(out)}>"
+    return f"{name}<{', '.join(out)}>"
 
 
 def main(prof_dir, out, n=512, lib_path="gcm_amd/lib/libgcmx.so", calib_json=None):
@@ -61,11 +69,11 @@ def main(prof_dir, out, n=512, lib_path="gcm_amd/lib/libgcmx.so", calib_json=Non
                            "write8_write_bytes": w8, "write_factor": wf},
            "kernels": {}}
     # bench.py's bucket "fused_xyz" is the one-pass step: k_step_tx2 (default) or
-    # k_fused_xyz; rows longer than 512 run the z split, k_step_tx2<2, 512, ..., ZS>
+    # the one-plane kernel (reported as k_fused_xyz); rows longer than 512 run the z split, k_step_tx2<2, 512, ..., ZS>
     # followed by k_zseam in the same bucket, so their bytes add up
     zsplit = ("fused_xyz", "k_step_tx2<2, 512, true, true, false, false, true", "k_zseam<2")
     for short, frag, *extra in (("march_x", "k_march<0, 2"), ("fused_yz", f"k_fused_yz<2, {z}"),
-                                ("fused_xyz", f"k_fused_xyz<2, {z}"), ("fused_xyz", f"k_step_tx2<2, {z}"),
+                                ("fused_xyz", f"k_step_plane<gcmx::IsoAxis, 2, {z}"), ("fused_xyz", f"k_step_tx2<2, {z}"),
                                 *((zsplit,) if n > 512 else ())):
         fks = [v for k, v in f.items() if frag in k]
         wks = [v for k, v in w.items() if frag in k]
