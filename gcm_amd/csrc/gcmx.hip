@@ -22,6 +22,7 @@
 #include "ortho.hpp"
 #include "acoustic.hpp"
 #include "observe.hpp"
+#include "setup.hpp"
 #include "plan.hpp"
 
 using namespace gcmx;
@@ -196,6 +197,8 @@ struct gcmx_ctx {
 	// of their outputs, grown to the largest request
 	void* obs_d = nullptr;
 	size_t obs_cap = 0;
+	// the set-up calls' tables (areas, vectors or ids) and census words (setup.hpp)
+	void* setup_d = nullptr;
 	// bytes the layer and observation calls copied (gcmx_transfer_stats)
 	uint64_t bytes_d2h = 0, bytes_h2d = 0;
 };
@@ -1455,6 +1458,7 @@ void gcmx_destroy(gcmx_ctx* c) {
 	(void)hipFree(c->nodes_d);
 	(void)hipFree(c->ode_d);
 	(void)hipFree(c->obs_d);
+	(void)hipFree(c->setup_d);
 	(void)hipFree(c->het_d);
 	(void)hipFree(c->ortho_het_d);
 	if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
@@ -1641,6 +1645,175 @@ gcmx_status gcmx_fill_random(gcmx_ctx* c, const int gs[3], uint64_t seed) {
 	launch_fill_random(c->cur, c->geo, st, D > 1 ? gs[1] : 1, D > 2 ? gs[2] : 1, seed, c->stream);
 	HIP_TRY(hipGetLastError());
 	touch_layer(c);
+	return GCMX_OK;
+}
+
+// ---- set-up by areas (setup.hpp) ------------------------------------------------
+
+namespace {
+
+// Everything a set-up call refuses, before anything changes; then the box by
+// role (a null box: every inner node with the context's own start).
+gcmx_status setup_check(const gcmx_ctx* c, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                        const void* table, SetupBox& bx) {
+	if (n < 1 || n > GCMX_MAX_SETUP_AREAS) return fail(GCMX_ERR_INVALID_ARG, "n must be 1..GCMX_MAX_SETUP_AREAS");
+	if (!areas || !table) return fail(GCMX_ERR_INVALID_ARG, "null table");
+	for (int k = 0; k < n; k++) {
+		const gcmx_area& a = areas[k];
+		int np = 0;
+		switch (a.kind) {
+		case GCMX_AREA_INFINITE: np = 0; break;
+		case GCMX_AREA_BOX: np = 6; break;
+		case GCMX_AREA_SPHERE: np = 4; break;
+		case GCMX_AREA_CYLINDER: np = 10; break;
+		default: return fail(GCMX_ERR_INVALID_ARG, "unknown area kind");
+		}
+		for (int i = 0; i < np; i++)
+			if (!std::isfinite(a.p[i])) return fail(GCMX_ERR_INVALID_ARG, "non-finite area parameter");
+		if ((a.kind == GCMX_AREA_SPHERE || a.kind == GCMX_AREA_CYLINDER) && !(a.p[0] > 0.0))
+			return fail(GCMX_ERR_INVALID_ARG, "area radius must be > 0");
+		if (a.kind == GCMX_AREA_BOX)
+			for (int i = 0; i < 3; i++)
+				if (!((a.p[3 + i] - a.p[i]) > 0.0)) return fail(GCMX_ERR_INVALID_ARG, "box area: max must exceed min");
+	}
+	int mn[3] = {0, 0, 0}, mx[3] = {1, 1, 1}, st[3] = {0, 0, 0};
+	for (int d = 0; d < c->D; d++) {
+		mn[d] = box ? box->min[d] : 0;
+		mx[d] = box ? box->max[d] : c->geo.sizes[d];
+		st[d] = box ? box->start[d] : c->desc.start[d];
+		if (mn[d] < 0 || mx[d] > c->geo.sizes[d]) return fail(GCMX_ERR_INVALID_ARG, "setup box outside the inner nodes");
+		if (mx[d] <= mn[d]) return fail(GCMX_ERR_INVALID_ARG, "empty setup box");
+	}
+	bx = make_setup_box(c->geo, mn, mx, st, c->desc.h);
+	return GCMX_OK;
+}
+
+// The call's tables on the device: the areas, then `extra`.  The stream's earlier
+// work may still read the buffer, so it is waited for first.
+gcmx_status setup_tables(gcmx_ctx* c, int n, const gcmx_area* areas, const void* extra, size_t extra_bytes,
+                         const char* what) {
+	if (!c->setup_d && hipMalloc(&c->setup_d, kSetupTableBytes + kCensusWords * sizeof(unsigned)) != hipSuccess) {
+		(void)hipGetLastError();
+		c->setup_d = nullptr;
+		return fail(GCMX_ERR_OOM, "device allocation failed");
+	}
+	// whole words: the kernels copy the tables into LDS as 64-bit words
+	std::vector<unsigned long long> words((size_t)n * kAreaWords + (extra_bytes + 7) / 8, 0ULL);
+	std::memcpy(words.data(), areas, (size_t)n * sizeof(gcmx_area));
+	std::memcpy(words.data() + (size_t)n * kAreaWords, extra, extra_bytes);
+	for (int k = 0; k < n; k++) reinterpret_cast<gcmx_area*>(words.data())[k].pad_ = 0;
+	gcmx_status s = wait_stream(c, c->stream, what);
+	if (s) return s;
+	HIP_TRY(hipMemcpy(c->setup_d, words.data(), words.size() * 8, hipMemcpyHostToDevice));
+	c->bytes_h2d += words.size() * 8;
+	return GCMX_OK;
+}
+
+unsigned* census_words(gcmx_ctx* c) {
+	return reinterpret_cast<unsigned*>(static_cast<char*>(c->setup_d) + kSetupTableBytes);
+}
+
+}  // namespace
+
+gcmx_status gcmx_setup_state(gcmx_ctx* c, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                             const double* vectors) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	SetupBox bx;
+	if ((s = setup_check(c, box, n, areas, vectors, bx)) != GCMX_OK) return s;
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	if ((s = setup_tables(c, n, areas, vectors, (size_t)n * c->M * sizeof(double), "gcmx_setup_state")) != GCMX_OK)
+		return s;
+	{
+		Timed t(c, "setup_state", (double)bx.na * bx.nb * bx.nf * c->M * sizeof(double), c->stream);
+		launch_setup_state(c->cur, c->geo, bx, n, static_cast<const unsigned long long*>(c->setup_d), c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	touch_layer(c);
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_setup_census(gcmx_ctx* c, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                              const uint8_t* id_of, uint32_t used[8]) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	SetupBox bx;
+	if ((s = setup_check(c, box, n, areas, id_of, bx)) != GCMX_OK) return s;
+	if (!used) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	if ((s = setup_tables(c, n, areas, id_of, (size_t)n, "gcmx_setup_census")) != GCMX_OK) return s;
+	{
+		Timed t(c, "setup_census", 0.0, c->stream);
+		launch_setup_ids(nullptr, c->geo, bx, n, static_cast<const unsigned long long*>(c->setup_d), census_words(c),
+		                 c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	if ((s = wait_stream(c, c->stream, "gcmx_setup_census")) != GCMX_OK) return s;
+	static_assert(sizeof(uint32_t) == sizeof(unsigned), "census words");
+	HIP_TRY(hipMemcpy(used, census_words(c), kCensusWords * sizeof(unsigned), hipMemcpyDeviceToHost));
+	c->bytes_d2h += kCensusWords * sizeof(unsigned);
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_setup_material_ids(gcmx_ctx* c, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                                    const uint8_t* id_of) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	SetupBox bx;
+	if ((s = setup_check(c, box, n, areas, id_of, bx)) != GCMX_OK) return s;
+	int mx = 0;
+	for (int k = 0; k < n; k++) {
+		if (c->n_mat > 0 && id_of[k] >= c->n_mat) return fail(GCMX_ERR_INVALID_ARG, "material id out of range");
+		mx = std::max(mx, (int)id_of[k]);
+	}
+	if ((s = setup_tables(c, n, areas, id_of, (size_t)n, "gcmx_setup_material_ids")) != GCMX_OK) return s;
+	if (!c->mat_d) {  // first use: every node material 0
+		uint8_t* ids = nullptr;
+		if (hipMalloc(&ids, (size_t)c->geo.n_inner) != hipSuccess) {
+			(void)hipGetLastError();
+			return fail(GCMX_ERR_OOM, "device allocation failed");
+		}
+		if (hipMemsetAsync(ids, 0, (size_t)c->geo.n_inner, c->stream) != hipSuccess) {
+			(void)hipFree(ids);
+			return fail(GCMX_ERR_HIP, "zero fill failed");
+		}
+		c->mat_d = ids;
+		c->max_mat_id = 0;
+	}
+	{
+		Timed t(c, "setup_ids", (double)bx.na * bx.nb * bx.nf, c->stream);
+		launch_setup_ids(c->mat_d, c->geo, bx, n, static_cast<const unsigned long long*>(c->setup_d), census_words(c),
+		                 c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	c->max_mat_id = std::max(c->max_mat_id, mx);
+	refresh_fast(c);
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_download_material_ids(gcmx_ctx* c, uint8_t* ids) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!ids) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	std::memset(ids, 0, (size_t)c->n_all);
+	if (!c->mat_d) return GCMX_OK;
+	const Geo& g = c->geo;
+	std::vector<uint8_t> inner((size_t)g.n_inner);
+	if ((s = wait_stream(c, c->stream, "gcmx_download_material_ids")) != GCMX_OK) return s;
+	HIP_TRY(hipMemcpy(inner.data(), c->mat_d, inner.size(), hipMemcpyDeviceToHost));
+	c->bytes_d2h += inner.size();
+	// the inverse of gcmx_set_material_ids' walk
+	long long i = 0;
+	for (int x = 0; x < g.sizes[0]; x++)
+		for (int y = 0; y < g.sizes[1]; y++)
+			for (int z = 0; z < g.sizes[2]; z++, i++) {
+				const int it[3] = {x, y, z};
+				long long ref = 0, mul = 1;
+				for (int d = c->D - 1; d >= 0; d--) {
+					ref += (it[d] + c->bs) * mul;
+					mul *= c->all_shape[d];
+				}
+				ids[ref] = inner[(size_t)i];
+			}
 	return GCMX_OK;
 }
 

@@ -32,6 +32,8 @@ MODEL_ELASTIC, MODEL_ACOUSTIC = 0, 1
 MODEL_NAMES = {MODEL_ELASTIC: "elastic", MODEL_ACOUSTIC: "acoustic"}
 UNIQUE_ID_BYTES = 128
 MAX_BORDER_Q = 16
+MAX_SETUP_AREAS = 256
+AREA_INFINITE, AREA_BOX, AREA_SPHERE, AREA_CYLINDER = 0, 1, 2, 3
 QUANTITY_CODES = {"Vx": 2, "Vy": 3, "Vz": 4, "Sxx": 5, "Sxy": 6, "Sxz": 7, "Syy": 8, "Syz": 9,
                   "Szz": 10, "PRESSURE": 12}
 
@@ -46,6 +48,7 @@ SYMBOLS = [
     "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_model_pde_size", "gcmx_status_string",
     "gcmx_create", "gcmx_create_model", "gcmx_get_model", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
     "gcmx_upload", "gcmx_download", "gcmx_fill_random",
+    "gcmx_setup_state", "gcmx_setup_census", "gcmx_setup_material_ids", "gcmx_download_material_ids",
     "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_scan",
     "gcmx_transfer_stats",
     "gcmx_stage", "gcmx_step",
@@ -98,6 +101,47 @@ class ScanResult(ctypes.Structure):
     _fields_ = [("nonfinite", ctypes.c_uint64), ("max_abs", ctypes.c_double * 9)]
 
 
+class Area(ctypes.Structure):
+    """gcmx_area (88 bytes): kind and parameters of one area of a set-up call."""
+    _fields_ = [("kind", ctypes.c_int), ("pad_", ctypes.c_int), ("p", ctypes.c_double * 10)]
+
+
+class SetupBox(ctypes.Structure):
+    """gcmx_setup_box: inner nodes [min, max) and the global index of the first."""
+    _fields_ = [("min", ctypes.c_int * 3), ("max", ctypes.c_int * 3), ("start", ctypes.c_int * 3)]
+
+
+def make_area(area) -> Area:
+    """An area tuple -- ("infinite",) | ("box", min3, max3) | ("sphere", r, c3) |
+    ("cylinder", r, b3, e3) -- as a gcmx_area.  The cylinder's axis is formed here
+    with the host constructor's operations (StraightBoundedCylinderArea: the
+    difference, its length by sqrt of the sum of squares, one division per entry)."""
+    if isinstance(area, Area):
+        return area
+    kind = area[0]
+    three = lambda v: [float(x) for x in list(v)[:3]] + [0.0] * (3 - len(list(v)[:3]))
+    a = Area()
+    if kind == "infinite":
+        a.kind = AREA_INFINITE
+    elif kind == "box":
+        a.kind = AREA_BOX
+        a.p[0:6] = three(area[1]) + three(area[2])
+    elif kind == "sphere":
+        a.kind = AREA_SPHERE
+        a.p[0:4] = [float(area[1])] + three(area[2])
+    elif kind == "cylinder":
+        a.kind = AREA_CYLINDER
+        b, e = np.array(three(area[2])), np.array(three(area[3]))
+        d = e - b
+        length = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            axis = d / length
+        a.p[0:10] = [float(area[1])] + list(b) + list(e) + [float(x) for x in axis]
+    else:
+        raise ValueError(f"unknown area kind {kind!r}")
+    return a
+
+
 class GridDesc(ctypes.Structure):
     _fields_ = [("dim", ctypes.c_int), ("border_size", ctypes.c_int),
                 ("sizes", ctypes.c_int * 3), ("start", ctypes.c_int * 3),
@@ -142,6 +186,13 @@ def lib() -> ctypes.CDLL:
     L.gcmx_upload.argtypes = [vp, dp]
     L.gcmx_download.argtypes = [vp, dp]
     L.gcmx_fill_random.argtypes = [vp, ip, ctypes.c_uint64]
+    # (the set-up calls by areas: bound when present, like the observation calls)
+    if hasattr(L, "gcmx_setup_state"):
+        ap, bp, u8p = ctypes.POINTER(Area), ctypes.POINTER(SetupBox), ctypes.POINTER(ctypes.c_uint8)
+        L.gcmx_setup_state.argtypes = [vp, bp, ctypes.c_int, ap, dp]
+        L.gcmx_setup_census.argtypes = [vp, bp, ctypes.c_int, ap, u8p, ctypes.POINTER(ctypes.c_uint32)]
+        L.gcmx_setup_material_ids.argtypes = [vp, bp, ctypes.c_int, ap, u8p]
+        L.gcmx_download_material_ids.argtypes = [vp, u8p]
     # (the observation calls: bound when present, like the round-5 additions below,
     # so that A/B timing runs can load an older build; tests/test_abi.py checks
     # this build exports them)
@@ -345,6 +396,51 @@ class Context:
     def download(self) -> np.ndarray:
         out = np.empty((self.n_all, self.M))
         _check(lib().gcmx_download(self._ptr, _dp(out)))
+        return out
+
+    # -- set-up by areas (no layer comes from the host) -----------------------
+    def _setup_args(self, areas, box):
+        arr = (Area * max(1, len(areas)))(*[make_area(a) for a in areas])
+        b = None
+        if box is not None:
+            pad = lambda v, fill: [int(x) for x in list(v)[:self.dim]] + [fill] * (3 - self.dim)
+            lo, hi, start = box
+            b = ctypes.byref(SetupBox((ctypes.c_int * 3)(*pad(lo, 0)), (ctypes.c_int * 3)(*pad(hi, 1)),
+                                      (ctypes.c_int * 3)(*pad(start, 0))))
+        return arr, b
+
+    def setup_state(self, areas, vectors, box=None):
+        """gcmx_setup_state: every node of `box` (None: all inner nodes, the
+        context's own start; else (min, max, start)) gets 0.0 plus vectors[k] for
+        each area k that holds it, in list order.  Areas: make_area's tuples."""
+        v = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1)
+        assert v.size == len(areas) * self.M
+        arr, b = self._setup_args(areas, box)
+        _check(lib().gcmx_setup_state(self._ptr, b, len(areas), arr, _dp(v) if v.size else None))
+
+    def setup_census(self, areas, id_of, box=None) -> np.ndarray:
+        """gcmx_setup_census: the sorted ids (id_of[k] of the last area holding a
+        node, 0 when none does) that occur in the box; writes nothing."""
+        ids = np.ascontiguousarray(id_of, dtype=np.uint8).reshape(-1)
+        assert ids.size == len(areas)
+        arr, b = self._setup_args(areas, box)
+        used = (ctypes.c_uint32 * 8)()
+        _check(lib().gcmx_setup_census(self._ptr, b, len(areas), arr,
+                                       ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if ids.size else None, used))
+        return np.array([v for v in range(256) if used[v >> 5] >> (v & 31) & 1], dtype=np.int64)
+
+    def setup_material_ids(self, areas, id_of, box=None):
+        """gcmx_setup_material_ids: the per-node material ids of the box, formed on the device."""
+        ids = np.ascontiguousarray(id_of, dtype=np.uint8).reshape(-1)
+        assert ids.size == len(areas)
+        arr, b = self._setup_args(areas, box)
+        _check(lib().gcmx_setup_material_ids(self._ptr, b, len(areas), arr,
+                                             ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if ids.size else None))
+
+    def material_ids(self) -> np.ndarray:
+        """gcmx_download_material_ids: uint8 per node of the all-nodes array, ghosts 0."""
+        out = np.zeros(self.shape_all, dtype=np.uint8)
+        _check(lib().gcmx_download_material_ids(self._ptr, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out
 
     # -- observation (no layer leaves the device) ---------------------------

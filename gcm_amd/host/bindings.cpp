@@ -351,6 +351,10 @@ PYBIND11_MODULE(_gcm_host, m) {
 	                  [](Task& t, int b) { t.cubicGrid.borderSize = b; })
 	    .def_property("h", [](Task& t) { return t.cubicGrid.h; },
 	                  [](Task& t, std::vector<real> h) { t.cubicGrid.h = h; })
+	    .def("set_device_setup", [](Task& t, bool on) { t.cubicGrid.setUpOnDevice = on; }, py::arg("on") = true,
+	         "Task::CubicGrid::setUpOnDevice: materials and initial state by areas on the device "
+	         "(gcmx_setup_*), no grid-sized host array; default off")
+	    .def_property_readonly("device_setup", [](Task& t) { return t.cubicGrid.setUpOnDevice; })
 	    .def("add_body",
 	         [](Task& t, size_t id, std::vector<int> sizes, std::vector<int> start, const std::string& model) {
 		         if (model != "elastic" && model != "acoustic") throw Exception("unknown model " + model);

@@ -187,37 +187,70 @@ HostState<D> HipMesh<D>::setUpMember(const Task& task) {
 }
 
 template <int D>
+typename HipMesh<D>::StackTable HipMesh<D>::stackTable(const std::vector<const HostState<D>*>& states) {
+	// one table over the members' material conditions; bitwise-equal ones shared
+	// (a stack of one material stays homogeneous: the non-HET one-pass step)
+	StackTable t;
+	t.remap.resize(states.size());
+	for (size_t k = 0; k < states.size(); k++)
+		for (size_t c = 0; c < states[k]->matrices.size(); c++) {
+			const GcmMatrices<D>& m = states[k]->matrices[c];
+			int found = -1;
+			for (size_t e = 0; e < t.table.size() && found < 0; e++)
+				if (std::memcmp(t.table[e], &m, sizeof(m)) == 0 && std::memcmp(&t.tau0[e], &states[k]->tau0[c], sizeof(real)) == 0)
+					found = (int)e;
+			if (found < 0) {
+				found = (int)t.table.size();
+				t.table.push_back(&m);
+				t.tau0.push_back(states[k]->tau0[c]);
+			}
+			t.remap[k].push_back(found);
+		}
+	if (t.table.size() > 255) throw Exception("a stack holds at most 255 materials");
+	return t;
+}
+
+template <int D>
+std::vector<int> HipMesh<D>::setStackMaterials(const StackTable& t, const std::vector<int>& used) {
+	const auto& table = t.table;
+	std::vector<int> dev(table.size(), -1);
+	int nUsed = 0;
+	for (size_t e = 0; e < table.size(); e++)
+		if (used[e]) dev[e] = nUsed++;
+	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
+	deviceTau0_.assign(nUsed, 0);
+	maximalEigenvalue = 0;
+	for (size_t e = 0; e < table.size(); e++) {
+		if (dev[e] < 0) continue;
+		deviceTau0_[dev[e]] = t.tau0[e];
+		maximalEigenvalue = std::fmax(maximalEigenvalue, table[e]->getMaximalEigenvalue());
+		for (int s = 0; s < D; s++) {
+			const size_t o = ((size_t)dev[e] * D + s);
+			std::copy(table[e]->m[s].U.begin(), table[e]->m[s].U.end(), U.begin() + o * M * M);
+			std::copy(table[e]->m[s].U1.begin(), table[e]->m[s].U1.end(), U1.begin() + o * M * M);
+			std::copy(table[e]->m[s].L.begin(), table[e]->m[s].L.end(), L.begin() + o * M);
+		}
+	}
+	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
+	return dev;
+}
+
+template <int D>
 void HipMesh<D>::setUpStack(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
                             const std::vector<HostState<D>>& states) {
 	if (pdeIsSetUp) throw Exception("setUpPde called twice");
 	pdeIsSetUp = true;
-	// one table over the members' material conditions; bitwise-equal ones shared
-	// (a stack of one material stays homogeneous: the non-HET one-pass step)
-	std::vector<const GcmMatrices<D>*> table;
-	std::vector<real> tau0;
-	std::vector<std::vector<int>> remap(members.size());
-	for (size_t k = 0; k < members.size(); k++)
-		for (size_t c = 0; c < states[k].matrices.size(); c++) {
-			const GcmMatrices<D>& m = states[k].matrices[c];
-			int found = -1;
-			for (size_t t = 0; t < table.size() && found < 0; t++)
-				if (std::memcmp(table[t], &m, sizeof(m)) == 0 && std::memcmp(&tau0[t], &states[k].tau0[c], sizeof(real)) == 0)
-					found = (int)t;
-			if (found < 0) {
-				found = (int)table.size();
-				table.push_back(&m);
-				tau0.push_back(states[k].tau0[c]);
-			}
-			remap[k].push_back(found);
-		}
-	if (table.size() > 255) throw Exception("a stack holds at most 255 materials");
+	std::vector<const HostState<D>*> sp;
+	for (const auto& st : states) sp.push_back(&st);
+	const StackTable tb = stackTable(sp);
+	const auto& remap = tb.remap;
 	// the stack's all-nodes state: every member's inner nodes and its ghost layers
 	// on the other axes; along the stack axis a member's ghost layers at a contact
 	// are its neighbour's inner layers (the stack's own ghosts only at its ends)
 	const int bs = this->borderSize, a = members.empty() ? 0 : members[0]->stackAxis_;
 	std::vector<real> pde((size_t)this->sizeOfAllNodes() * M, 0.0);
 	std::vector<uint8_t> ids((size_t)this->sizeOfAllNodes(), 0);
-	std::vector<int> used(table.size(), 0);
+	std::vector<int> used(tb.table.size(), 0);
 	for (size_t k = 0; k < members.size(); k++) {
 		const HipMesh<D>& mb = *members[k];
 		forEachAll<D>(mb.sizes, bs, [&](const IntD& it) {
@@ -233,30 +266,229 @@ void HipMesh<D>::setUpStack(const std::vector<std::shared_ptr<HipMesh<D>>>& memb
 			if (inner) used[(size_t)t] = 1;
 		});
 	}
-	std::vector<int> dev(table.size(), -1);
-	int nUsed = 0;
-	for (size_t t = 0; t < table.size(); t++)
-		if (used[t]) dev[t] = nUsed++;
-	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
-	deviceTau0_.assign(nUsed, 0);
-	maximalEigenvalue = 0;
-	for (size_t t = 0; t < table.size(); t++) {
-		if (dev[t] < 0) continue;
-		deviceTau0_[dev[t]] = tau0[t];
-		maximalEigenvalue = std::fmax(maximalEigenvalue, table[t]->getMaximalEigenvalue());
-		for (int s = 0; s < D; s++) {
-			const size_t o = ((size_t)dev[t] * D + s);
-			std::copy(table[t]->m[s].U.begin(), table[t]->m[s].U.end(), U.begin() + o * M * M);
-			std::copy(table[t]->m[s].U1.begin(), table[t]->m[s].U1.end(), U1.begin() + o * M * M);
-			std::copy(table[t]->m[s].L.begin(), table[t]->m[s].L.end(), L.begin() + o * M);
-		}
-	}
-	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
-	if (nUsed > 1) {
+	const std::vector<int> dev = setStackMaterials(tb, used);
+	if (deviceTau0_.size() > 1) {
 		for (auto& m : ids) m = (uint8_t)std::max(0, dev[m]);
 		gcmxCheck(gcmx_set_material_ids(ctx_, ids.data()), "gcmx_set_material_ids");
 	}
 	gcmxCheck(gcmx_upload(ctx_, pde.data()), "gcmx_upload");
+}
+
+// ------------------------------------------------------- set-up on the device --
+
+gcmx_area deviceArea(const Area& area) {
+	gcmx_area a{};
+	if (dynamic_cast<const InfiniteArea*>(&area)) {
+		a.kind = GCMX_AREA_INFINITE;
+	} else if (const auto* b = dynamic_cast<const AxisAlignedBoxArea*>(&area)) {
+		a.kind = GCMX_AREA_BOX;
+		for (int i = 0; i < 3; i++) {
+			a.p[i] = b->min[i];
+			a.p[3 + i] = b->max[i];
+		}
+	} else if (const auto* s = dynamic_cast<const SphereArea*>(&area)) {
+		a.kind = GCMX_AREA_SPHERE;
+		a.p[0] = s->radius;
+		for (int i = 0; i < 3; i++) a.p[1 + i] = s->center[i];
+	} else if (const auto* c = dynamic_cast<const StraightBoundedCylinderArea*>(&area)) {
+		a.kind = GCMX_AREA_CYLINDER;
+		a.p[0] = c->radius;
+		for (int i = 0; i < 3; i++) {
+			a.p[1 + i] = c->begin[i];
+			a.p[4 + i] = c->end[i];
+			a.p[7 + i] = c->axis[i];
+		}
+	} else {
+		throw Exception("set-up on the device: an Area of a kind the device does not know");
+	}
+	return a;
+}
+
+namespace {
+
+std::vector<gcmx_area> deviceAreas(const std::vector<std::shared_ptr<Area>>& areas) {
+	std::vector<gcmx_area> out;
+	for (const auto& a : areas) {
+		if (!a) throw Exception("set-up on the device: a condition without an area");
+		out.push_back(deviceArea(*a));
+	}
+	return out;
+}
+
+/// gcmx_setup_state for the (area, vector) pairs of a body; no pair: the layer
+/// keeps the zeros it was created with.
+template <int D>
+void deviceInitialState(gcmx_ctx* ctx, const gcmx_setup_box* box, const SetUpLists<D>& ls) {
+	if (ls.initial.empty()) return;
+	std::vector<gcmx_area> areas;
+	std::vector<real> vectors;
+	for (const auto& ic : ls.initial) {
+		if (!ic.first) throw Exception("set-up on the device: a condition without an area");
+		areas.push_back(deviceArea(*ic.first));
+		vectors.insert(vectors.end(), ic.second.begin(), ic.second.begin() + ls.st.M);
+	}
+	gcmxCheck(gcmx_setup_state(ctx, box, (int)areas.size(), areas.data(), vectors.data()), "gcmx_setup_state");
+}
+
+/// The ids (entries of `idOf`) that occur in the box, as flags.
+std::vector<int> deviceCensus(gcmx_ctx* ctx, const gcmx_setup_box* box, const std::vector<gcmx_area>& areas,
+                              const std::vector<uint8_t>& idOf, size_t nIds) {
+	uint32_t mask[8] = {};
+	gcmxCheck(gcmx_setup_census(ctx, box, (int)areas.size(), areas.data(), idOf.data(), mask), "gcmx_setup_census");
+	std::vector<int> used(nIds, 0);
+	for (size_t v = 0; v < nIds && v < 256; v++) used[v] = (mask[v >> 5] >> (v & 31)) & 1;
+	return used;
+}
+
+}  // namespace
+
+template <int D>
+gcmx_setup_box HipMesh<D>::setupBox(int axis, int offset) const {
+	gcmx_setup_box b{};
+	for (int d = 0; d < 3; d++) {
+		b.min[d] = 0;
+		b.max[d] = d < D ? this->sizes[d] : 1;
+		b.start[d] = d < D ? this->start[d] : 0;
+	}
+	if (axis >= 0) {
+		b.min[axis] += offset;
+		b.max[axis] += offset;
+	}
+	return b;
+}
+
+template <int D>
+void HipMesh<D>::setUpPdeOnDevice(const Task& task) {
+	SetUpLists<D> ls = buildSetUpLists<D>(task, *this);
+	const HostState<D>& st = ls.st;
+	if (st.model != model_) throw Exception("the body's model changed after its mesh was created");
+	matrices = st.matrices;
+	acousticMatrices = st.acousticMatrices;
+	maximalEigenvalue = st.maximalEigenvalue;
+	materialNumbers_ = st.materialNumber;
+	const size_t nCond = st.numberOfConditions();
+	const int M = st.M;
+
+	// ---- device tables: only the materials the nodes actually use (the census)
+	const std::vector<gcmx_area> areas = deviceAreas(ls.materialAreas);
+	std::vector<uint8_t> idOf(nCond);
+	for (size_t c = 0; c < nCond; c++) idOf[c] = (uint8_t)c;
+	const std::vector<int> used = deviceCensus(ctx_, nullptr, areas, idOf, nCond);
+	std::vector<int> remap(nCond, -1);
+	int nUsed = 0;
+	for (size_t c = 0; c < nCond; c++)
+		if (used[c]) remap[c] = nUsed++;
+	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
+	deviceTau0_.assign(nUsed, 0);
+	for (size_t c = 0; c < nCond; c++) {
+		if (remap[c] < 0) continue;
+		deviceTau0_[remap[c]] = st.tau0[c];
+		for (int s = 0; s < D; s++) {
+			const size_t o = ((size_t)remap[c] * D + s);
+			if (model_ == Models::T::ACOUSTIC) {
+				const auto& m = acousticMatrices[c].m[s];
+				std::copy(m.U.begin(), m.U.end(), U.begin() + o * M * M);
+				std::copy(m.U1.begin(), m.U1.end(), U1.begin() + o * M * M);
+				std::copy(m.L.begin(), m.L.end(), L.begin() + o * M);
+				continue;
+			}
+			std::copy(matrices[c].m[s].U.begin(), matrices[c].m[s].U.end(), U.begin() + o * M * M);
+			std::copy(matrices[c].m[s].U1.begin(), matrices[c].m[s].U1.end(), U1.begin() + o * M * M);
+			std::copy(matrices[c].m[s].L.begin(), matrices[c].m[s].L.end(), L.begin() + o * M);
+		}
+	}
+	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
+	if (nUsed > 1) {
+		for (size_t c = 0; c < nCond; c++) idOf[c] = (uint8_t)std::max(0, remap[c]);
+		gcmxCheck(gcmx_setup_material_ids(ctx_, nullptr, (int)areas.size(), areas.data(), idOf.data()),
+		          "gcmx_setup_material_ids");
+	}
+	deviceInitialState<D>(ctx_, nullptr, ls);
+	if (nCond > 1) {  // the snapshotters' material array: from the device on first use
+		idsOnDevice_ = true;
+		materialAreas_ = ls.materialAreas;
+		conditionOfDeviceId_.assign(256, -1);
+		for (size_t c = 0; c < nCond; c++)
+			if (remap[c] >= 0) conditionOfDeviceId_[(size_t)remap[c]] = (int)c;
+	}
+}
+
+template <int D>
+SetUpLists<D> HipMesh<D>::setUpMemberOnDevice(const Task& task) {
+	if (pdeIsSetUp) throw Exception("setUpPde called twice");
+	pdeIsSetUp = true;
+	SetUpLists<D> ls = buildSetUpLists<D>(task, *this);
+	matrices = ls.st.matrices;
+	maximalEigenvalue = ls.st.maximalEigenvalue;
+	materialNumbers_ = ls.st.materialNumber;
+	return ls;
+}
+
+template <int D>
+void HipMesh<D>::setUpStackOnDevice(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
+                                    const std::vector<SetUpLists<D>>& lists) {
+	if (pdeIsSetUp) throw Exception("setUpPde called twice");
+	pdeIsSetUp = true;
+	std::vector<const HostState<D>*> sp;
+	for (const auto& ls : lists) sp.push_back(&ls.st);
+	const StackTable tb = stackTable(sp);
+	// every member's census over its own box of the stack, with its own start: the
+	// stack's ghosts and the contact layers need nothing beyond the members' inner nodes
+	std::vector<int> used(tb.table.size(), 0);
+	std::vector<std::vector<gcmx_area>> areas(members.size());
+	std::vector<gcmx_setup_box> boxes(members.size());
+	for (size_t k = 0; k < members.size(); k++) {
+		const HipMesh<D>& mb = *members[k];
+		areas[k] = deviceAreas(lists[k].materialAreas);
+		boxes[k] = mb.setupBox(mb.stackAxis_, mb.stackOffset_);
+		std::vector<uint8_t> idOf;
+		for (int t : tb.remap[k]) idOf.push_back((uint8_t)t);
+		const std::vector<int> mine = deviceCensus(ctx_, &boxes[k], areas[k], idOf, tb.table.size());
+		for (size_t t = 0; t < used.size(); t++) used[t] = used[t] || mine[t];
+	}
+	const std::vector<int> dev = setStackMaterials(tb, used);
+	for (size_t k = 0; k < members.size(); k++) {
+		HipMesh<D>& mb = *members[k];
+		if (deviceTau0_.size() > 1) {
+			std::vector<uint8_t> idOf;
+			for (int t : tb.remap[k]) idOf.push_back((uint8_t)std::max(0, dev[(size_t)t]));
+			gcmxCheck(gcmx_setup_material_ids(ctx_, &boxes[k], (int)areas[k].size(), areas[k].data(), idOf.data()),
+			          "gcmx_setup_material_ids");
+		}
+		deviceInitialState<D>(ctx_, &boxes[k], lists[k]);
+		if (mb.matrices.size() > 1) {
+			mb.idsOnDevice_ = true;
+			mb.materialAreas_ = lists[k].materialAreas;
+			mb.conditionOfDeviceId_.assign(256, -1);
+			for (size_t c = 0; c < tb.remap[k].size(); c++) {
+				const int d = dev[(size_t)tb.remap[k][c]];
+				if (d < 0) continue;
+				int& slot = mb.conditionOfDeviceId_[(size_t)d];
+				slot = slot == -1 ? (int)c : -2;  // two conditions of one material: the device cannot tell them apart
+			}
+		}
+	}
+}
+
+template <int D>
+void HipMesh<D>::fetchMaterialIds() const {
+	idsOnDevice_ = false;
+	const HipMesh<D>& owner = stack_ ? *stack_ : *this;  // whose context holds the ids
+	std::vector<uint8_t> all((size_t)owner.sizeOfAllNodes());
+	gcmxCheck(gcmx_download_material_ids(ctx_, all.data()), "gcmx_download_material_ids");
+	matIdAll_.assign((size_t)this->sizeOfAllNodes(), 0);
+	forEachInner<D>(this->sizes, [&](const IntD& it) {
+		IntD is = it;
+		if (stack_) is[stackAxis_] += stackOffset_;
+		int c = conditionOfDeviceId_[all[(size_t)owner.getIndex(is)]];
+		if (c == -2) {  // MaterialsCondition::apply for this node on the host
+			const Real3 x = this->coords(it);
+			for (size_t k = 0; k < materialAreas_.size(); k++)
+				if (materialAreas_[k]->contains(x)) c = (int)k;
+		}
+		if (c < 0) throw Exception("a node's device material id names no material condition");
+		matIdAll_[(size_t)this->getIndex(it)] = (uint8_t)c;
+	});
 }
 
 template <int D>
@@ -279,19 +511,43 @@ typename CubicGrid<D>::ConstructionPack constructionPack(const Task& task, size_
 // the data would be stored, without touching a GPU.
 template <int D>
 HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
+	SetUpLists<D> ls = buildSetUpLists<D>(task, grid);
+	HostState<D> st = std::move(ls.st);
+	const int M = st.M;
+	const long long nAll = grid.sizeOfAllNodes();
+	st.pde.assign((size_t)nAll * M, 0.0);
+	st.matId.assign((size_t)nAll, 0);
+	auto& pde = st.pde;
+	auto& matId = st.matId;
+	// ---- MaterialsCondition::apply, the node loop (MaterialsCondition.hpp:23-36)
+	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
+		const Real3 x = grid.coords(it);
+		for (size_t c = 0; c < ls.materialAreas.size(); c++)
+			if (ls.materialAreas[c]->contains(x)) matId[(size_t)grid.getIndex(it)] = (uint8_t)c;
+	});
+	// ---- InitialCondition::apply, the node loop (InitialCondition.hpp:23-88)
+	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
+		const Real3 x = grid.coords(it);
+		real* v = &pde[(size_t)grid.getIndex(it) * M];
+		for (int c = 0; c < M; c++) v[c] = 0;
+		for (const auto& ic : ls.initial)
+			if (ic.first->contains(x))
+				for (int c = 0; c < M; c++) v[c] += ic.second[c];
+	});
+	return st;
+}
+
+template <int D>
+SetUpLists<D> buildSetUpLists(const Task& task, const CubicGrid<D>& grid) {
 	constexpr int MX = pdeSize(D);  // the elastic vector; the acoustic one (D + 1) is no longer
-	HostState<D> st;
+	SetUpLists<D> ls;
+	HostState<D>& st = ls.st;
 	const auto body = task.bodies.find(grid.id);
 	const Models::T model = body != task.bodies.end() ? body->second.modelId : Models::T::ELASTIC;
 	const bool acoustic = model == Models::T::ACOUSTIC;
 	const int M = pdeSizeOf(model, D);
 	st.model = model;
 	st.M = M;
-	const long long nAll = grid.sizeOfAllNodes();
-	st.pde.assign((size_t)nAll * M, 0.0);
-	st.matId.assign((size_t)nAll, 0);
-	auto& pde = st.pde;
-	auto& matId = st.matId;
 	auto& matrices = st.matrices;
 
 	// ---- MaterialsCondition::apply (util/task/MaterialsCondition.hpp:23-36, 70-91)
@@ -344,11 +600,7 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 			st.materialNumber.push_back(conds[c].iso->materialNumber);
 		}
 	}
-	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
-		const Real3 x = grid.coords(it);
-		for (size_t c = 0; c < conds.size(); c++)
-			if (conds[c].first->contains(x)) matId[(size_t)grid.getIndex(it)] = (uint8_t)c;
-	});
+	for (const Cond& c : conds) ls.materialAreas.push_back(c.first);
 	st.maximalEigenvalue = 0;
 	for (const auto& m : matrices)
 		st.maximalEigenvalue = std::fmax(st.maximalEigenvalue, m.getMaximalEigenvalue());
@@ -356,7 +608,7 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 		st.maximalEigenvalue = std::fmax(st.maximalEigenvalue, m.getMaximalEigenvalue());
 
 	// ---- InitialCondition::apply (util/task/InitialCondition.hpp:23-88)
-	std::vector<std::pair<std::shared_ptr<Area>, std::array<real, MX>>> ics;  // the first M entries
+	auto& ics = ls.initial;  // the first M entries
 	for (const auto& v : task.initialCondition.vectors) {
 		if ((int)v.list.size() != M) throw Exception("initial vector has the wrong size");
 		std::array<real, MX> a{};
@@ -386,21 +638,14 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 		else setQuantity(D, q.physicalQuantity, q.value, tmp.data());
 		ics.push_back({q.area, tmp});
 	}
-	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
-		const Real3 x = grid.coords(it);
-		real* v = &pde[(size_t)grid.getIndex(it) * M];
-		for (int c = 0; c < M; c++) v[c] = 0;
-		for (const auto& ic : ics)
-			if (ic.first->contains(x))
-				for (int c = 0; c < M; c++) v[c] += ic.second[c];
-	});
-	return st;
+	return ls;
 }
 
 template <int D>
 void HipMesh<D>::setUpPde(const Task& task) {
 	if (pdeIsSetUp) throw Exception("setUpPde called twice");
 	pdeIsSetUp = true;
+	if (task.cubicGrid.setUpOnDevice) return setUpPdeOnDevice(task);
 	HostState<D> st = buildHostState<D>(task, *this);
 	if (st.model != model_) throw Exception("the body's model changed after its mesh was created");
 	matrices = st.matrices;
@@ -697,10 +942,14 @@ Engine<D>::Engine(const Task& task, int device_) : AbstractEngine(task), device(
 	if (task.globalSettings.dimensionality != D) throw Exception("dimensionality mismatch");
 	createGridsAndContacts(task);
 	buildStacks(task);
+	const bool onDevice = task.cubicGrid.setUpOnDevice;
 	std::map<size_t, HostState<D>> memberStates;
+	std::map<size_t, SetUpLists<D>> memberLists;
 	for (const auto& tb : task.bodies) {
 		Body& body = getBody(tb.first);
-		if (body.stack)
+		if (body.stack && onDevice)
+			memberLists.emplace(tb.first, std::dynamic_pointer_cast<HipMesh<D>>(body.mesh)->setUpMemberOnDevice(task));
+		else if (body.stack)
 			memberStates.emplace(tb.first, std::dynamic_pointer_cast<HipMesh<D>>(body.mesh)->setUpMember(task));
 		else
 			body.mesh->setUpPde(task);
@@ -714,11 +963,14 @@ Engine<D>::Engine(const Task& task, int device_) : AbstractEngine(task), device(
 		if (!lead.stackLead) continue;
 		std::vector<std::shared_ptr<HipMesh<D>>> members;
 		std::vector<HostState<D>> states;
+		std::vector<SetUpLists<D>> lists;
 		for (size_t id : stackOrder_.at(lead.mesh->id)) {
 			members.push_back(std::dynamic_pointer_cast<HipMesh<D>>(getBody(id).mesh));
-			states.push_back(std::move(memberStates.at(id)));
+			if (onDevice) lists.push_back(std::move(memberLists.at(id)));
+			else states.push_back(std::move(memberStates.at(id)));
 		}
-		lead.stack->setUpStack(members, states);
+		if (onDevice) lead.stack->setUpStackOnDevice(members, lists);
+		else lead.stack->setUpStack(members, states);
 	}
 	afterConstruction(task);
 }
@@ -1168,6 +1420,9 @@ template CubicGrid<3>::ConstructionPack constructionPack<3>(const Task&, size_t)
 template HostState<1> buildHostState<1>(const Task&, const CubicGrid<1>&);
 template HostState<2> buildHostState<2>(const Task&, const CubicGrid<2>&);
 template HostState<3> buildHostState<3>(const Task&, const CubicGrid<3>&);
+template SetUpLists<1> buildSetUpLists<1>(const Task&, const CubicGrid<1>&);
+template SetUpLists<2> buildSetUpLists<2>(const Task&, const CubicGrid<2>&);
+template SetUpLists<3> buildSetUpLists<3>(const Task&, const CubicGrid<3>&);
 template class Engine<1>;
 template class Engine<2>;
 template class Engine<3>;

@@ -146,6 +146,23 @@ typename CubicGrid<D>::ConstructionPack constructionPack(const Task& task, size_
 template <int D>
 HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid);
 
+/// The per-condition half of buildHostState: its HostState without the per-node
+/// arrays (`pde` and `matId` empty), and the two lists its node loops apply --
+/// the area of every material condition, and the (area, vector) pairs of
+/// InitialCondition::apply in the reference's order: vectors, waves, quantities
+/// (the first M entries of a vector count).
+template <int D>
+struct SetUpLists {
+	HostState<D> st;
+	std::vector<std::shared_ptr<Area>> materialAreas;
+	std::vector<std::pair<std::shared_ptr<Area>, std::array<real, pdeSize(D)>>> initial;
+};
+template <int D>
+SetUpLists<D> buildSetUpLists(const Task& task, const CubicGrid<D>& grid);
+
+/// An Area as the device knows it (gcmx_area); throws for a kind it does not.
+gcmx_area deviceArea(const Area& area);
+
 /// DefaultMesh's role with GPU-resident storage: the context owns both time
 /// layers on the device; the host holds only set-up data.
 template <int D>
@@ -197,7 +214,12 @@ public:
 	const std::vector<real>& deviceTau0() const { return deviceTau0_; }
 	/// Material-condition index per node (all-nodes order) and the conditions'
 	/// IsotropicMaterial::materialNumber (DefaultMesh::material(it), for snapshots).
-	const std::vector<uint8_t>& materialIdsAll() const { return matIdAll_; }
+	/// After a set-up on the device (Task::CubicGrid::setUpOnDevice) the ids come
+	/// from the device on first use (gcmx_download_material_ids).
+	const std::vector<uint8_t>& materialIdsAll() const {
+		if (idsOnDevice_) fetchMaterialIds();
+		return matIdAll_;
+	}
 	const std::vector<int>& materialNumbers() const { return materialNumbers_; }
 
 	/// STACKS.  3-D bodies stacked along y or z whose every contact is an adhesion
@@ -217,6 +239,11 @@ public:
 	/// The stack's set-up from its members' host states, members in stack order.
 	void setUpStack(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
 	                const std::vector<HostState<D>>& states);
+	/// The same two with the node loops on the device: a member keeps its lists,
+	/// the stack runs census, ids and state once per member over the member's box.
+	SetUpLists<D> setUpMemberOnDevice(const Task& task);
+	void setUpStackOnDevice(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
+	                        const std::vector<SetUpLists<D>>& lists);
 
 private:
 	std::shared_ptr<HipMesh<D>> stack_;  // set for a stack member
@@ -229,9 +256,27 @@ private:
 	Models::T model_ = Models::T::ELASTIC;
 	std::vector<AcousticMatrices<D>> acousticMatrices;  // the same for an acoustic body
 	std::vector<real> deviceTau0_;
-	std::vector<uint8_t> matIdAll_;
+	mutable std::vector<uint8_t> matIdAll_;
 	std::vector<int> materialNumbers_;
 	bool pdeIsSetUp = false;
+	// set-up on the device: the ids wait on the device until a snapshot asks
+	void setUpPdeOnDevice(const Task& task);
+	void fetchMaterialIds() const;
+	/// This mesh's inner nodes as a box of its context, `offset` nodes along `axis`
+	/// (a stack member's place in the stack; axis < 0: none), with its own start.
+	gcmx_setup_box setupBox(int axis, int offset) const;
+	/// One table over the members' material conditions, bitwise-equal ones shared.
+	struct StackTable {
+		std::vector<const GcmMatrices<D>*> table;
+		std::vector<real> tau0;
+		std::vector<std::vector<int>> remap;  // [member][condition] -> table entry
+	};
+	static StackTable stackTable(const std::vector<const HostState<D>*>& states);
+	/// The used entries of a stack's table to the device; table entry -> device id or -1.
+	std::vector<int> setStackMaterials(const StackTable& t, const std::vector<int>& used);
+	mutable bool idsOnDevice_ = false;
+	std::vector<std::shared_ptr<Area>> materialAreas_;  // per condition, for fetchMaterialIds
+	std::vector<int> conditionOfDeviceId_;               // device id -> condition, -1: none, -2: several
 };
 
 /// engine/cubic/GridCharacteristicMethod.hpp:13-17

@@ -198,6 +198,10 @@ struct Task {
 		std::vector<real> h;
 		int borderSize = 0;
 		std::map<size_t, Cube> cubics;
+		/// Host only: MaterialsCondition::apply and InitialCondition::apply run on the
+		/// device (gcmx_setup_*), and set-up allocates nothing the size of the grid
+		/// on the host.  The results are those of the host loops, bitwise.
+		bool setUpOnDevice = false;
 	} cubicGrid;
 
 	/// Every condition holds a material of either kind: `material` (isotropic) or

@@ -170,6 +170,68 @@ gcmx_status gcmx_download(gcmx_ctx* ctx, double* aos_all_nodes);
  * box of `global_sizes` nodes; ghosts untouched.  Generated on the device. */
 gcmx_status gcmx_fill_random(gcmx_ctx* ctx, const int global_sizes[3], uint64_t seed);
 
+/* ---- set-up by areas, on the device -------------------------------------------
+ * Replaces the two node loops of DefaultMesh::setUpPde (DefaultMesh.hpp:60-66):
+ * MaterialsCondition::apply (util/task/MaterialsCondition.hpp:23-36) and
+ * InitialCondition::apply (util/task/InitialCondition.hpp:23-88) as kernels that
+ * only write, so that set-up moves the small tables below and no layer.  Both
+ * are functions of a node's coordinates, CubicGrid::coords bitwise
+ * ((double)start[i] * h[i] + (double)it[i] * h[i], 0.0 for axes >= dim), and of
+ * Area::contains (util/math/Area.hpp:8-120), restated with the host's roundings;
+ * every kind is strict, a node on the surface is outside.
+ *   BOX:      p[0..2] min, p[3..5] max.
+ *   SPHERE:   p[0] radius, p[1..3] center.
+ *   CYLINDER: p[0] radius, p[1..3] begin, p[4..6] end, p[7..9] axis: the unit
+ *             vector (end - begin) / |end - begin| as the caller formed it (the
+ *             device does not divide).
+ * For axes >= dim a node's coordinate is 0.0 and an area is tested there too. */
+typedef enum gcmx_area_kind {
+	GCMX_AREA_INFINITE = 0,
+	GCMX_AREA_BOX = 1,
+	GCMX_AREA_SPHERE = 2,
+	GCMX_AREA_CYLINDER = 3
+} gcmx_area_kind;
+typedef struct gcmx_area {
+	int    kind; /* gcmx_area_kind */
+	int    pad_;
+	double p[10];
+} gcmx_area; /* 88 bytes */
+/* The inner nodes [min, max) of the context a call covers (entries >= dim are
+ * ignored), and `start`, the global index of the box's first node: node `it` of
+ * the box has the coordinates of local node it - min of a grid that starts
+ * there.  Bodies stacked into one context each fill their own box with their
+ * own start.  A NULL box is every inner node with the context's own start. */
+typedef struct gcmx_setup_box {
+	int min[3], max[3];
+	int start[3];
+} gcmx_setup_box;
+#define GCMX_MAX_SETUP_AREAS 256
+/* Every call: n in 1..GCMX_MAX_SETUP_AREAS; an unknown kind, a non-finite
+ * parameter, a radius <= 0, a box area whose max <= min, an empty setup box or
+ * one outside the inner nodes, or a null table is GCMX_ERR_INVALID_ARG and
+ * changes nothing.  Only the tables are copied to the device
+ * (gcmx_transfer_stats counts them).
+ *
+ * gcmx_setup_state: each node of the box gets v = 0.0, then v += vectors[k] for
+ * every area k that holds it, in list order (vectors: [n][M]); ghosts and nodes
+ * outside the box keep their values.  Asynchronous on the context's stream, like
+ * gcmx_fill_random. */
+gcmx_status gcmx_setup_state(gcmx_ctx* ctx, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                             const double* vectors);
+/* used: bit v of word v / 32 is set when some node of the box would get id v,
+ * that is id_of[k] of the LAST area k that holds it, 0 when none does.  Writes
+ * nothing to the context; synchronous. */
+gcmx_status gcmx_setup_census(gcmx_ctx* ctx, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                              const uint8_t* id_of, uint32_t used[8]);
+/* gcmx_set_material_ids with the ids formed on the device: the box's nodes get
+ * the id above.  The first call allocates the id array with every node 0.  An
+ * id_of entry >= n_mat once materials are set is GCMX_ERR_INVALID_ARG. */
+gcmx_status gcmx_setup_material_ids(gcmx_ctx* ctx, const gcmx_setup_box* box, int n, const gcmx_area* areas,
+                                    const uint8_t* id_of);
+/* The per-node ids as gcmx_set_material_ids takes them (one byte per node of the
+ * all-nodes array, ghost entries 0); all 0 when the context has none. */
+gcmx_status gcmx_download_material_ids(gcmx_ctx* ctx, uint8_t* ids_all_nodes);
+
 /* ---- observation -------------------------------------------------------------
  * What a snapshotter or a detector needs from the current layer, formed on the
  * device: no call here moves a layer.  Replaces the reads of
