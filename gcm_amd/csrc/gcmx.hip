@@ -23,6 +23,7 @@
 #include "acoustic.hpp"
 #include "observe.hpp"
 #include "setup.hpp"
+#include "state.hpp"
 #include "plan.hpp"
 
 using namespace gcmx;
@@ -1626,6 +1627,100 @@ gcmx_status gcmx_download(gcmx_ctx* c, double* aos) {
 	HIP_TRY(hipMemcpy(soa.data(), c->cur, c->layer_elems * sizeof(double), hipMemcpyDeviceToHost));
 	c->bytes_d2h += c->layer_elems * sizeof(double);
 	soa_to_aos(c, soa.data(), aos);
+	return GCMX_OK;
+}
+
+// ---- the state by boxes (state.hpp) ----------------------------------------------
+
+namespace {
+
+gcmx_status observe_staging(gcmx_ctx* c, size_t bytes);
+
+constexpr size_t kStateStageDefault = (size_t)256 << 20;
+
+// Everything a box call refuses, before anything changes; then the box by role.
+// `reach`: how far the box may reach into the ghosts.
+gcmx_status state_check(const gcmx_ctx* c, const int bmin[3], const int bmax[3], const void* aos, int reach,
+                        StateBox& bx) {
+	if (!bmin || !bmax) return fail(GCMX_ERR_INVALID_ARG, "null box");
+	if (!aos) return fail(GCMX_ERR_INVALID_ARG, "null host array");
+	int mn[3] = {0, 0, 0}, mx[3] = {1, 1, 1};
+	for (int d = 0; d < c->D; d++) {
+		mn[d] = bmin[d];
+		mx[d] = bmax[d];
+		if (mn[d] < -reach || mx[d] > c->geo.sizes[d] + reach)
+			return fail(GCMX_ERR_INVALID_ARG, reach ? "box outside the nodes of the layer" : "box outside the inner nodes");
+		if (mx[d] <= mn[d]) return fail(GCMX_ERR_INVALID_ARG, "empty box");
+	}
+	bx = make_state_box(c->geo, mn, mx);
+	return GCMX_OK;
+}
+
+// Rows of one chunk: what `stage_bytes` holds, one row at least, and no more
+// than the box has or one launch takes.
+long long state_chunk_rows(const gcmx_ctx* c, const StateBox& bx, size_t stage_bytes) {
+	const size_t row_bytes = (size_t)bx.nf * c->M * sizeof(double);
+	const size_t cap = stage_bytes ? stage_bytes : kStateStageDefault;
+	long long rows = std::max<long long>(1, (long long)(cap / row_bytes));
+	rows = std::min(rows, (long long)bx.na * bx.nb);
+	return std::min(rows, state_max_rows(bx));
+}
+
+}  // namespace
+
+gcmx_status gcmx_read_box(gcmx_ctx* c, const int bmin[3], const int bmax[3], double* aos, size_t stage_bytes) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	StateBox bx;
+	if ((s = state_check(c, bmin, bmax, aos, c->bs, bx)) != GCMX_OK) return s;
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	const long long total = (long long)bx.na * bx.nb, chunk = state_chunk_rows(c, bx, stage_bytes);
+	const size_t row_elems = (size_t)bx.nf * c->M;
+	if ((s = observe_staging(c, (size_t)chunk * row_elems * sizeof(double))) != GCMX_OK) return s;
+	double* stage = static_cast<double*>(c->obs_d);
+	for (long long r0 = 0; r0 < total; r0 += chunk) {
+		const long long rows = std::min(chunk, total - r0);
+		const size_t bytes = (size_t)rows * row_elems * sizeof(double);
+		{
+			Timed t(c, "state_pack", 2.0 * (double)bytes, c->stream);
+			if (!launch_state_pack(c->cur, c->M, bx, r0, rows, stage, c->stream))
+				return fail(GCMX_ERR_UNSUPPORTED, "no state kernel for this PDE size");
+			HIP_TRY(hipGetLastError());
+		}
+		if ((s = wait_stream(c, c->stream, "gcmx_read_box")) != GCMX_OK) return s;
+		HIP_TRY(hipMemcpy(aos + (size_t)r0 * row_elems, stage, bytes, hipMemcpyDeviceToHost));
+		c->bytes_d2h += bytes;
+	}
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_write_box(gcmx_ctx* c, const int bmin[3], const int bmax[3], const double* aos, size_t stage_bytes) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	StateBox bx;
+	if ((s = state_check(c, bmin, bmax, aos, 0, bx)) != GCMX_OK) return s;
+	if ((s = halo_wait(c)) != GCMX_OK) return s;
+	const long long total = (long long)bx.na * bx.nb, chunk = state_chunk_rows(c, bx, stage_bytes);
+	const size_t row_elems = (size_t)bx.nf * c->M;
+	if ((s = observe_staging(c, (size_t)chunk * row_elems * sizeof(double))) != GCMX_OK) return s;
+	double* stage = static_cast<double*>(c->obs_d);
+	// the stream's work done: nothing still reads the staging or writes the layer
+	if ((s = wait_stream(c, c->stream, "gcmx_write_box")) != GCMX_OK) return s;
+	for (long long r0 = 0; r0 < total; r0 += chunk) {
+		const long long rows = std::min(chunk, total - r0);
+		const size_t bytes = (size_t)rows * row_elems * sizeof(double);
+		HIP_TRY(hipMemcpy(stage, aos + (size_t)r0 * row_elems, bytes, hipMemcpyHostToDevice));
+		c->bytes_h2d += bytes;
+		touch_layer(c);
+		{
+			Timed t(c, "state_unpack", 2.0 * (double)bytes, c->stream);
+			if (!launch_state_unpack(c->cur, c->M, bx, r0, rows, stage, c->stream))
+				return fail(GCMX_ERR_UNSUPPORTED, "no state kernel for this PDE size");
+			HIP_TRY(hipGetLastError());
+		}
+		// the next chunk's copy overwrites the staging this kernel reads
+		if ((s = wait_stream(c, c->stream, "gcmx_write_box")) != GCMX_OK) return s;
+	}
 	return GCMX_OK;
 }
 

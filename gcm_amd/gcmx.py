@@ -47,7 +47,7 @@ def Q_COMPONENT(c: int) -> int:
 SYMBOLS = [
     "gcmx_abi_version", "gcmx_last_error", "gcmx_pde_size", "gcmx_model_pde_size", "gcmx_status_string",
     "gcmx_create", "gcmx_create_model", "gcmx_get_model", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
-    "gcmx_upload", "gcmx_download", "gcmx_fill_random",
+    "gcmx_upload", "gcmx_download", "gcmx_read_box", "gcmx_write_box", "gcmx_fill_random",
     "gcmx_setup_state", "gcmx_setup_census", "gcmx_setup_material_ids", "gcmx_download_material_ids",
     "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_scan",
     "gcmx_transfer_stats",
@@ -185,6 +185,10 @@ def lib() -> ctypes.CDLL:
     L.gcmx_set_material_ids.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
     L.gcmx_upload.argtypes = [vp, dp]
     L.gcmx_download.argtypes = [vp, dp]
+    # (the state by boxes: bound when present, like the calls below)
+    if hasattr(L, "gcmx_read_box"):
+        L.gcmx_read_box.argtypes = [vp, ip, ip, dp, ctypes.c_size_t]
+        L.gcmx_write_box.argtypes = [vp, ip, ip, dp, ctypes.c_size_t]
     L.gcmx_fill_random.argtypes = [vp, ip, ctypes.c_uint64]
     # (the set-up calls by areas: bound when present, like the observation calls)
     if hasattr(L, "gcmx_setup_state"):
@@ -397,6 +401,34 @@ class Context:
         out = np.empty((self.n_all, self.M))
         _check(lib().gcmx_download(self._ptr, _dp(out)))
         return out
+
+    # -- the exact state by boxes (the device transposes; no layer-sized host copy) --
+    def _box(self, box_min, box_max):
+        pad = lambda v, fill: [int(x) for x in list(v)[:self.dim]] + [fill] * (3 - self.dim)
+        lo, hi = pad(box_min, 0), pad(box_max, 1)
+        return lo, hi, tuple(b - a for a, b in zip(lo[:self.dim], hi[:self.dim]))
+
+    def read_box(self, box_min: Sequence[int], box_max: Sequence[int], out: Optional[np.ndarray] = None,
+                 stage_bytes: int = 0) -> np.ndarray:
+        """gcmx_read_box: the fp64 state of the nodes [box_min, box_max) (inner
+        indices; may reach border_size into the ghosts) as [*box, M], bit for bit.
+        `out`: a C-contiguous float64 array of that size to fill."""
+        lo, hi, ext = self._box(box_min, box_max)
+        shape = tuple(max(0, e) for e in ext) + (self.M,)
+        if out is None:
+            out = np.empty(shape)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size == int(np.prod(shape))
+        _check(lib().gcmx_read_box(self._ptr, _ip(lo), _ip(hi), _dp(out), int(stage_bytes)))
+        return out.reshape(shape)
+
+    def write_box(self, box_min: Sequence[int], array: np.ndarray, stage_bytes: int = 0):
+        """gcmx_write_box: `array` ([*box, M], float64) becomes the state of the inner
+        nodes [box_min, box_min + box); nothing else changes."""
+        a = np.ascontiguousarray(array, dtype=np.float64)
+        assert a.ndim == self.dim + 1 and a.shape[-1] == self.M
+        hi = [int(m) + n for m, n in zip(list(box_min)[:self.dim], a.shape[:self.dim])]
+        lo, hi, _ = self._box(box_min, hi)
+        _check(lib().gcmx_write_box(self._ptr, _ip(lo), _ip(hi), _dp(a), int(stage_bytes)))
 
     # -- set-up by areas (no layer comes from the host) -----------------------
     def _setup_args(self, areas, box):

@@ -45,6 +45,30 @@ PhysicalQuantities::T quantity(const std::string& q) {
 	return it->second;
 }
 
+/// (id, "elastic" | "acoustic", M, sizes) as a body of a state file
+StateFileBody stateBody(const py::tuple& t) {
+	StateFileBody b;
+	b.id = t[0].cast<uint64_t>();
+	const std::string model = t[1].cast<std::string>();
+	if (model == "elastic") b.model = Models::T::ELASTIC;
+	else if (model == "acoustic") b.model = Models::T::ACOUSTIC;
+	else throw Exception("unknown model " + model);
+	b.M = t[2].cast<uint32_t>();
+	const auto sizes = t[3].cast<std::vector<uint32_t>>();
+	for (size_t d = 0; d < 3 && d < sizes.size(); d++) b.sizes[d] = sizes[d];
+	return b;
+}
+
+StateFileHeader stateHeader(uint32_t D, int64_t steps, real time, real timeStep, const std::vector<py::tuple>& bodies) {
+	StateFileHeader h;
+	h.D = D;
+	h.steps = steps;
+	h.time = time;
+	h.timeStep = timeStep;
+	for (const py::tuple& t : bodies) h.bodies.push_back(stateBody(t));
+	return h;
+}
+
 Waves::T wave(const std::string& w) {
 	static const std::map<std::string, Waves::T> m = {
 	    {"P_FORWARD", Waves::T::P_FORWARD},   {"P_BACKWARD", Waves::T::P_BACKWARD},
@@ -434,6 +458,13 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         })
 	    .def("set_vtk_chunk_bytes", [](Task& t, size_t bytes) { t.vtkSnapshotter.chunkBytes = bytes; },
 	         "most output bytes one device request of the cubic VtkSnapshotter carries (default 256 MiB)")
+	    .def("set_checkpoint",
+	         [](Task& t, const std::string& directory, int steps) {
+		         t.checkpoint.directory = directory;
+		         t.checkpoint.stepsPerCheckpoint = steps;
+	         },
+	         py::arg("directory"), py::arg("steps"),
+	         "run() saves the engine's state to directory/checkpoint.gcmx after every steps-th step (0: never)")
 	    .def("set_detector",
 	         [](Task& t, std::vector<std::string> qs, py::tuple area, size_t gridId) {
 		         t.detector.quantities.clear();
@@ -711,6 +742,54 @@ PYBIND11_MODULE(_gcm_host, m) {
 	    "determinant (b None) or solution of A x = b through csrc/contact.hpp's GSL LU restatement",
 	    py::arg("A"), py::arg("b") = py::none());
 
+	// the GPU-free half of the engine's state file (state_file.hpp); a body is
+	// (id, "elastic" | "acoustic", M, sizes)
+	m.def(
+	    "state_file_offsets",
+	    [](uint32_t D, const std::vector<py::tuple>& bodies) { return stateFileOffsets(stateHeader(D, 0, 0, 0, bodies)); },
+	    "byte offset of every body's nodes in a state file, then the file's size", py::arg("D"), py::arg("bodies"));
+	m.def(
+	    "state_file_read",
+	    [](const std::string& path) {
+		    const StateFileHeader h = readStateFileHeader(path);
+		    py::list bodies;
+		    for (const StateFileBody& b : h.bodies) {
+			    std::vector<uint32_t> sizes(b.sizes.begin(), b.sizes.begin() + h.D);
+			    bodies.append(py::make_tuple(b.id, b.model == Models::T::ACOUSTIC ? "acoustic" : "elastic", b.M, sizes));
+		    }
+		    py::dict d;
+		    d["D"] = h.D;
+		    d["steps"] = h.steps;
+		    d["time"] = h.time;
+		    d["time_step"] = h.timeStep;
+		    d["bodies"] = bodies;
+		    d["offsets"] = stateFileOffsets(h);
+		    return d;
+	    },
+	    "parse a state file's header and records and check them against its size", py::arg("path"));
+	m.def(
+	    "state_file_check",
+	    [](const std::string& path, uint32_t D, const std::vector<py::tuple>& bodies) {
+		    checkStateFileHeader(readStateFileHeader(path), stateHeader(D, 0, 0, 0, bodies));
+	    },
+	    "what Engine.load_state refuses, without an engine: the file against D and the bodies", py::arg("path"),
+	    py::arg("D"), py::arg("bodies"));
+	py::class_<StateFileWriter>(m, "StateFileWriter")
+	    .def(py::init<const std::string&>(), py::arg("path"))
+	    .def_property_readonly("temporary_path", &StateFileWriter::temporaryPath)
+	    .def_property_readonly("written", &StateFileWriter::written)
+	    .def("write_header",
+	         [](StateFileWriter& w, uint32_t D, int64_t steps, real time, real timeStep, const std::vector<py::tuple>& bodies) {
+		         w.writeHeader(stateHeader(D, steps, time, timeStep, bodies));
+	         },
+	         py::arg("D"), py::arg("steps"), py::arg("time"), py::arg("time_step"), py::arg("bodies"))
+	    .def("write_body_record", [](StateFileWriter& w, const py::tuple& body) { w.writeBodyRecord(stateBody(body)); })
+	    .def("write",
+	         [](StateFileWriter& w, py::array_t<real, py::array::c_style | py::array::forcecast> a) {
+		         w.write(a.data(), (size_t)a.size() * sizeof(real));
+	         })
+	    .def("commit", &StateFileWriter::commit);
+
 	m.def("simplex_plans", &simplexPlans,
 	      "GPU-free simplex set-up: mesh, time step, gradient and stage plans", py::arg("task"));
 
@@ -767,6 +846,14 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         py::arg("task"), py::arg("device") = 0)
 	    .def("run", [](PyEngine& p) { p.e->run(); })
 	    .def("run_steps", &PyEngine::runSteps)
+	    // (long file I/O and no Python callback inside: other Python threads may run)
+	    .def("save_state", [](PyEngine& p, const std::string& path) { p.e->saveState(path); }, py::arg("path"),
+	         py::call_guard<py::gil_scoped_release>(),
+	         "the exact state of every body, the step count and the clock to a file (written under a temporary name, then renamed)")
+	    .def("load_state", [](PyEngine& p, const std::string& path) { p.e->loadState(path); }, py::arg("path"),
+	         py::call_guard<py::gil_scoped_release>(),
+	         "restore a saved state into an engine built from the same task; a mismatch raises and changes nothing")
+	    .def_property_readonly("checkpoint_file", [](PyEngine& p) { return p.e->checkpointFile(); })
 	    .def("pde", &PyEngine::pde, "current layer of a body, all nodes incl. ghosts [..., M]")
 	    .def("path", &PyEngine::path)
 	    .def("last_path", &PyEngine::lastPath)

@@ -21,8 +21,23 @@ void gcmxCheck(gcmx_status s, const char* what) {
 // ------------------------------------------------------------ AbstractEngine --
 
 AbstractEngine::AbstractEngine(const Task& task)
-    : CourantNumber(task.globalSettings.CourantNumber) {
+    : CourantNumber(task.globalSettings.CourantNumber), checkpoint(task.checkpoint) {
 	Clock::setZero();
+}
+
+void AbstractEngine::saveState(const std::string&) const { throw Exception("saveState: only the cubic engine saves its state"); }
+void AbstractEngine::loadState(const std::string&) { throw Exception("loadState: only the cubic engine loads a state"); }
+
+std::string AbstractEngine::checkpointFile() const {
+	if (checkpoint.stepsPerCheckpoint <= 0) return "";
+	return (checkpoint.directory.empty() ? std::string(".") : checkpoint.directory) + "/checkpoint.gcmx";
+}
+
+void AbstractEngine::restoreClock(int steps_, real time, real timeStep) {
+	steps = steps_;
+	Clock::time = time;
+	Clock::timeStep = timeStep;
+	resumed = true;
 }
 
 // AbstractEngine.cpp:18-27
@@ -36,8 +51,12 @@ void AbstractEngine::afterConstruction(const Task& task) {
 
 // AbstractEngine.cpp:30-46
 void AbstractEngine::run() {
-	int step = 0;
-	writeSnapshots(step);
+	// after loadState the saved run goes on: its step numbers, and no second
+	// snapshot of the step it was saved at
+	int step = resumed ? steps : 0;
+	if (!resumed) writeSnapshots(step);
+	resumed = false;
+	const std::string file = checkpointFile();
 	while (Clock::Time() < requiredTime) {
 		Clock::timeStep = estimateTimeStep();
 		nextTimeStep();
@@ -45,6 +64,7 @@ void AbstractEngine::run() {
 		steps++;
 		Clock::tickTack();
 		writeSnapshots(step);
+		if (!file.empty() && step % checkpoint.stepsPerCheckpoint == 0) saveState(file);
 	}
 }
 
@@ -693,22 +713,41 @@ void HipMesh<D>::setUpPde(const Task& task) {
 
 template <int D>
 std::vector<real> HipMesh<D>::pdeAll() const {
-	const int M = pdeM();
-	std::vector<real> out((size_t)this->sizeOfAllNodes() * M);
-	if (stack_) {  // this member's part of the stack (its ghost layers at a contact:
-		           // the neighbour's inner layers, as the contact copy leaves them)
-		const std::vector<real> all = stack_->pdeAll();
-		const int bs = this->borderSize;
-		forEachAll<D>(this->sizes, bs, [&](const IntD& it) {
-			IntD is = it;
-			is[stackAxis_] += stackOffset_;
-			const size_t src = (size_t)stack_->getIndex(is), dst = (size_t)this->getIndex(it);
-			for (int c = 0; c < M; c++) out[dst * M + c] = all[src * M + c];
-		});
-		return out;
+	// the all-nodes box; for a stack member its part of the stack (its ghost layers
+	// at a contact: the neighbour's inner layers, as the contact copy leaves them)
+	std::vector<real> out((size_t)this->sizeOfAllNodes() * pdeM());
+	IntD lo, hi;
+	for (int d = 0; d < D; d++) {
+		lo[d] = -this->borderSize;
+		hi[d] = this->sizes[d] + this->borderSize;
 	}
-	gcmxCheck(gcmx_download(ctx_, out.data()), "gcmx_download");
+	readBox(lo, hi, out.data());
 	return out;
+}
+
+template <int D>
+void HipMesh<D>::readBox(const IntD& boxMin, const IntD& boxMax, real* aos, size_t stageBytes) const {
+	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
+	for (int d = 0; d < D; d++) {
+		if (boxMin[d] < -this->borderSize || boxMax[d] > this->sizes[d] + this->borderSize)
+			throw Exception("readBox: box outside the nodes of the mesh");
+		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
+		lo[d] = boxMin[d] + off;
+		hi[d] = boxMax[d] + off;
+	}
+	gcmxCheck(gcmx_read_box(ctx_, lo, hi, aos, stageBytes), "gcmx_read_box");
+}
+
+template <int D>
+void HipMesh<D>::writeBox(const IntD& boxMin, const IntD& boxMax, const real* aos, size_t stageBytes) {
+	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
+	for (int d = 0; d < D; d++) {
+		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("writeBox: only inner nodes can be written");
+		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
+		lo[d] = boxMin[d] + off;
+		hi[d] = boxMax[d] + off;
+	}
+	gcmxCheck(gcmx_write_box(ctx_, lo, hi, aos, stageBytes), "gcmx_write_box");
 }
 
 template <int D>
@@ -938,7 +977,8 @@ void HipContactCopier<D>::apply(HipMesh<D>& a, const HipMesh<D>& b) const {
 // --------------------------------------------------------------------- Engine --
 
 template <int D>
-Engine<D>::Engine(const Task& task, int device_) : AbstractEngine(task), device(device_) {
+Engine<D>::Engine(const Task& task, int device_)
+    : AbstractEngine(task), device(device_), stateChunkBytes(task.vtkSnapshotter.chunkBytes) {
 	if (task.globalSettings.dimensionality != D) throw Exception("dimensionality mismatch");
 	createGridsAndContacts(task);
 	buildStacks(task);
@@ -1260,6 +1300,90 @@ template <int D>
 void Engine<D>::writeSnapshots(const int step) {
 	for (Body& body : bodies)
 		for (auto& snap : body.snapshotters) snap->snapshot(body.mesh.get(), step);
+}
+
+// ------------------------------------------------------------ save and resume --
+
+template <int D>
+StateFileHeader Engine<D>::stateHeader() const {
+	StateFileHeader h;
+	h.D = D;
+	h.steps = steps;
+	h.time = Clock::Time();
+	h.timeStep = Clock::TimeStep();
+	for (const Body& body : bodies) {
+		const HipMesh<D>& mesh = dynamic_cast<const HipMesh<D>&>(*body.mesh);
+		StateFileBody b;
+		b.id = mesh.id;
+		b.model = mesh.model();
+		b.M = (uint32_t)mesh.pdeM();
+		for (int d = 0; d < D; d++) b.sizes[d] = (uint32_t)mesh.sizes[d];
+		h.bodies.push_back(b);
+	}
+	return h;
+}
+
+namespace {
+
+// Slabs along x of the inner nodes of `sizes`: at most chunkBytes each, one x
+// plane at least.  f(lo, hi, bytes of the slab).
+template <int D, typename F>
+void forEachStateSlab(const std::array<int, D>& sizes, int M, size_t chunkBytes, F f) {
+	size_t plane = (size_t)M * sizeof(real);
+	for (int d = 1; d < D; d++) plane *= (size_t)sizes[d];
+	const int thick = (int)std::min<size_t>((size_t)sizes[0], std::max<size_t>(1, chunkBytes / plane));
+	for (int x0 = 0; x0 < sizes[0]; x0 += thick) {
+		std::array<int, D> lo{}, hi = sizes;
+		lo[0] = x0;
+		hi[0] = std::min(x0 + thick, sizes[0]);
+		f(lo, hi, (size_t)(hi[0] - x0) * plane);
+	}
+}
+
+}  // namespace
+
+template <int D>
+void Engine<D>::saveState(const std::string& path) const {
+	const StateFileHeader h = stateHeader();
+	StateFileWriter w(path);
+	w.writeHeader(h);
+	std::vector<real> slab;  // one slab, never a layer
+	for (size_t k = 0; k < bodies.size(); k++) {
+		const HipMesh<D>& mesh = dynamic_cast<const HipMesh<D>&>(*bodies[k].mesh);
+		w.writeBodyRecord(h.bodies[k]);
+		forEachStateSlab<D>(mesh.sizes, mesh.pdeM(), stateChunkBytes, [&](const auto& lo, const auto& hi, size_t bytes) {
+			slab.resize(bytes / sizeof(real));
+			mesh.readBox(lo, hi, slab.data(), stateChunkBytes);
+			w.write(slab.data(), bytes);
+		});
+	}
+	if (w.written() != stateFileOffsets(h).back()) throw Exception("saveState: wrote another size than the header says");
+	w.commit();
+}
+
+template <int D>
+void Engine<D>::loadState(const std::string& path) {
+	// everything that can be refused, before the first node changes
+	const StateFileHeader file = readStateFileHeader(path);
+	checkStateFileHeader(file, stateHeader());
+	const std::vector<uint64_t> offsets = stateFileOffsets(file);
+	std::FILE* f = std::fopen(path.c_str(), "rb");
+	if (!f) throw Exception("state file " + path + ": cannot open");
+	struct Close {
+		std::FILE* f;
+		~Close() { std::fclose(f); }
+	} closer{f};
+	std::vector<real> slab;
+	for (size_t k = 0; k < bodies.size(); k++) {
+		HipMesh<D>& mesh = dynamic_cast<HipMesh<D>&>(*bodies[k].mesh);
+		if (std::fseek(f, (long)offsets[k], SEEK_SET) != 0) throw Exception("state file " + path + ": cannot seek");
+		forEachStateSlab<D>(mesh.sizes, mesh.pdeM(), stateChunkBytes, [&](const auto& lo, const auto& hi, size_t bytes) {
+			slab.resize(bytes / sizeof(real));
+			if (std::fread(slab.data(), 1, bytes, f) != bytes) throw Exception("state file " + path + ": read failed");
+			mesh.writeBox(lo, hi, slab.data(), stateChunkBytes);
+		});
+	}
+	restoreClock((int)file.steps, file.time, file.timeStep);
 }
 
 // ------------------------------------------------------------- snapshotters --

@@ -15,11 +15,13 @@
 
 #include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/gcmx.h"
 #include "acoustic_model.hpp"
 #include "snapshot.hpp"
+#include "state_file.hpp"
 #include "task.hpp"
 
 namespace gcm {
@@ -53,11 +55,23 @@ public:
 	void runSteps(int n);
 	int stepsDone() const { return steps; }
 	real getRequiredTime() const { return requiredTime; }
+	/// The exact state of every body with the step count and the clock, to a file
+	/// and back (state_file.hpp).  After loadState, run() continues the saved run:
+	/// its step numbers go on from the restored count and the restored step's
+	/// snapshots are not written again.  The cubic engine implements them.
+	virtual void saveState(const std::string& path) const;
+	virtual void loadState(const std::string& path);
+	/// The file run() saves to (Task::Checkpoint); empty: none.
+	std::string checkpointFile() const;
 
 protected:
 	const real CourantNumber = 0;
 	real requiredTime = 0;
 	int steps = 0;
+	const Task::Checkpoint checkpoint;
+	bool resumed = false;  // loadState restored `steps` and the clock; run() has not continued yet
+	/// loadState's last act: the step count and the clock of the saved run.
+	void restoreClock(int steps_, real time, real timeStep);
 	void afterConstruction(const Task& task);
 	virtual void nextTimeStep() = 0;
 	virtual real estimateTimeStep() = 0;
@@ -183,8 +197,17 @@ public:
 	/// The device swap happens inside gcmx_stage; nothing to do here.
 	void swapCurrAndNextPdeTimeLayer(int) override {}
 	gcmx_ctx* ctx() const { return ctx_; }
-	/// Current layer in the reference AoS all-nodes order (downloads).
+	/// Current layer in the reference AoS all-nodes order: readBox of the all-nodes
+	/// box (a stack member reads its own part of the stack, no more).
 	std::vector<real> pdeAll() const;
+	/// The exact fp64 state of the nodes [boxMin, boxMax) as [node][pdeM()] in the
+	/// reference's node order (gcmx_read_box / gcmx_write_box).  readBox may reach
+	/// borderSize into the ghosts; writeBox takes inner nodes only and changes
+	/// nothing else.  A stack member addresses the stack's context with its own
+	/// offset, as snapshotArrays does.  stageBytes: bound of the device staging (0:
+	/// the library's default).
+	void readBox(const IntD& boxMin, const IntD& boxMax, real* aos, size_t stageBytes = 0) const;
+	void writeBox(const IntD& boxMin, const IntD& boxMax, const real* aos, size_t stageBytes = 0);
 	/// One node's PDE vector (gathers its pdeM() components on the device); an
 	/// acoustic body fills the first pdeM() entries.
 	std::array<real, M> pde(const IntD& it) const;
@@ -482,6 +505,13 @@ public:
 	typedef CubicGrid<D> Grid;
 	explicit Engine(const Task& task, int device = 0);
 	std::shared_ptr<const HipMesh<D>> getMesh(size_t gridId) const;
+	/// saveState streams every body's inner nodes in slabs along x of at most
+	/// Task::vtkSnapshotter.chunkBytes (one x plane at least) through readBox to a
+	/// temporary file and renames it; loadState validates the whole file against
+	/// the engine's bodies first (a mismatch throws and leaves the engine as it
+	/// was), then streams writeBox and restores the step count and the clock.
+	void saveState(const std::string& path) const override;
+	void loadState(const std::string& path) override;
 
 protected:
 	void nextTimeStep() override;
@@ -516,6 +546,8 @@ private:
 	/// none (the other members of a stack).
 	HipMesh<D>* unitMesh(Body& b);
 	void applyOdes();
+	const size_t stateChunkBytes;  // Task::vtkSnapshotter.chunkBytes
+	StateFileHeader stateHeader() const;
 };
 
 }  // namespace cubic

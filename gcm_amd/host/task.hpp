@@ -318,6 +318,14 @@ struct Task {
 		size_t chunkBytes = 256u << 20;
 	} vtkSnapshotter;
 
+	/// Host only: run() of the cubic engine saves its state (Engine::saveState) after
+	/// the snapshots of every stepsPerCheckpoint-th step to the one file
+	/// directory/checkpoint.gcmx, each save replacing the one before.  0: never.
+	struct Checkpoint {
+		std::string directory;
+		int stepsPerCheckpoint = 0;
+	} checkpoint;
+
 	struct Detector {
 		std::vector<PhysicalQuantities::T> quantities;
 		std::shared_ptr<Area> area;

@@ -165,6 +165,40 @@ gcmx_status gcmx_set_material_ids(gcmx_ctx* ctx, const uint8_t* ids_all_nodes);
 /* Whole current time layer, host <-> device (DefaultMesh::pdeVariables). */
 gcmx_status gcmx_upload(gcmx_ctx* ctx, const double* aos_all_nodes);
 gcmx_status gcmx_download(gcmx_ctx* ctx, double* aos_all_nodes);
+/* The exact fp64 state of a box of the current layer, host <-> device
+ * (DefaultMesh::pdeVariables by box).  aos: [node][M], nodes of the box in the
+ * reference's order (x slowest, last axis fastest), M = gcmx_model_pde_size(model,
+ * dim).  Entries >= dim of the box are ignored.  Pure moves: every one of the 64
+ * bits of every value arrives unchanged (-0.0, subnormals, infinities, NaNs with
+ * their payloads); the transposition between the component planes and [node][M]
+ * runs on the device (k_state_pack / k_state_unpack).
+ * A call works through the box in chunks of consecutive rows (a row: the box's
+ * nodes along the last axis), each one contiguous range of `aos`: one kernel
+ * launch and one copy of exactly the chunk's bytes per chunk, so the library
+ * allocates no host memory proportional to the box.  stage_bytes: upper bound of
+ * the device staging one call uses (0: 256 MiB; never less than one row of the
+ * box); the staging belongs to the context and is freed by gcmx_destroy.
+ * gcmx_transfer_stats counts exactly nodes * M * 8 bytes per call.
+ * An empty box, a box outside the allowed range or a null buffer is
+ * GCMX_ERR_INVALID_ARG and changes nothing.
+ *
+ * gcmx_read_box: box coordinates are inner-node indices and may reach into the
+ * ghosts, -border_size <= min < max <= sizes + border_size per axis; the all-nodes
+ * box reproduces gcmx_download bit for bit.  Synchronous like gcmx_download (a
+ * pending halo exchange, then the stream's work complete first); changes no
+ * state of the context.
+ *
+ * gcmx_write_box: inner nodes only, 0 <= min < max <= sizes (a box that reaches a
+ * ghost is GCMX_ERR_INVALID_ARG).  Writes the current layer's box and nothing
+ * else: ghosts, nodes outside the box and the other layer keep their bits, and
+ * what decides the step's path (ghost writes, face fills) stays as it is, so a
+ * context that would take the one-pass step still does.  Synchronous.  On a slab
+ * context the neighbours' halo planes become stale until the next exchange,
+ * exactly as after gcmx_upload. */
+gcmx_status gcmx_read_box(gcmx_ctx* ctx, const int box_min[3], const int box_max[3], double* aos,
+                          size_t stage_bytes);
+gcmx_status gcmx_write_box(gcmx_ctx* ctx, const int box_min[3], const int box_max[3], const double* aos,
+                           size_t stage_bytes);
 /* "parity-random" field: every inner component uniform in
  * [-1,1) from SplitMix64(seed), indexed in global (x,y,z,c) order of a global
  * box of `global_sizes` nodes; ghosts untouched.  Generated on the device. */
@@ -280,8 +314,8 @@ typedef struct gcmx_scan_result {
 } gcmx_scan_result;
 gcmx_status gcmx_scan(gcmx_ctx* ctx, gcmx_scan_result* out);
 /* out[0] / out[1]: bytes copied device -> host / host -> device since
- * gcmx_create by gcmx_upload, gcmx_download and the observation calls (node
- * lists included). */
+ * gcmx_create by gcmx_upload, gcmx_download, the box calls and the observation
+ * calls (node lists included). */
 gcmx_status gcmx_transfer_stats(gcmx_ctx* ctx, uint64_t out[2]);
 
 /* ---- the hot path ------------------------------------------------------------
