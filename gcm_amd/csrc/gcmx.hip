@@ -2034,19 +2034,31 @@ gcmx_status gcmx_gather(gcmx_ctx* c, const gcmx_node_list* h, int n_q, const int
 	return observe_fetch(c, out, 0, bytes);
 }
 
-gcmx_status gcmx_snapshot_box(gcmx_ctx* c, const int bmin_[3], const int bmax_[3], int want_velocity, int n_q,
-                              const int* qs, float* velocity, float* out) {
+namespace {
+
+// gcmx_snapshot_box (step == nullptr: every node, the unit-stride kernel) and
+// gcmx_snapshot_strided (every step[d]-th node from the box minimum).
+gcmx_status snapshot_impl(gcmx_ctx* c, const int bmin_[3], const int bmax_[3], const int* step_, int want_velocity,
+                          int n_q, const int* qs, float* velocity, float* out, const char* what) {
 	gcmx_status s = check_ctx(c);
 	if (s) return s;
 	if (!bmin_ || !bmax_) return fail(GCMX_ERR_INVALID_ARG, "null box");
-	int bmin[3] = {0, 0, 0}, bmax[3] = {1, 1, 1};
+	int bmin[3] = {0, 0, 0}, bmax[3] = {1, 1, 1}, step[3] = {1, 1, 1}, np[3] = {1, 1, 1};
 	long long n = 1;
+	bool unit = true;
 	for (int d = 0; d < c->D; d++) {
 		bmin[d] = bmin_[d];
 		bmax[d] = bmax_[d];
 		if (bmin[d] < 0 || bmax[d] > c->geo.sizes[d]) return fail(GCMX_ERR_INVALID_ARG, "box outside the inner nodes");
 		if (bmax[d] <= bmin[d]) return fail(GCMX_ERR_INVALID_ARG, "empty box");
-		n *= bmax[d] - bmin[d];
+		if (step_) {
+			if (step_[d] < 1) return fail(GCMX_ERR_INVALID_ARG, "a stride is at least 1");
+			step[d] = step_[d];
+		}
+		const int extent = bmax[d] - bmin[d];
+		np[d] = (int)(((long long)extent + step[d] - 1) / step[d]);
+		unit = unit && step[d] == 1;
+		n *= np[d];
 	}
 	ObserveQ oq;
 	if ((s = observe_q(c, n_q, qs, 0, oq)) != GCMX_OK) return s;
@@ -2059,18 +2071,41 @@ gcmx_status gcmx_snapshot_box(gcmx_ctx* c, const int bmin_[3], const int bmax_[3
 	float* vel_d = want_velocity ? static_cast<float*>(c->obs_d) : nullptr;
 	float* q_d = reinterpret_cast<float*>(static_cast<char*>(c->obs_d) + vel_bytes);
 	{
-		// algorithmic bytes: the fp64 planes read (Velocity's D, a trace's D, else 1) and the Float32 written
+		// algorithmic bytes: the fp64 planes read (Velocity's D, a trace's D, else 1) and the Float32 written;
+		// a strided box reads whole 128-byte lines of its selected rows (pack_strided_traffic)
 		double planes = want_velocity ? c->D : 0;
 		for (int k = 0; k < n_q; k++) planes += oq.comp[k] == kObservePressure ? c->D : 1;
-		Timed t(c, "pack_vtk", (double)n * planes * sizeof(double) + (double)(vel_bytes + q_bytes), c->stream);
-		launch_pack_vtk(c->cur, c->geo, bmin, bmax, vel_d, oq, q_d, c->stream);
-		HIP_TRY(hipGetLastError());
+		if (unit) {
+			Timed t(c, "pack_vtk", (double)n * planes * sizeof(double) + (double)(vel_bytes + q_bytes), c->stream);
+			launch_pack_vtk(c->cur, c->geo, bmin, bmax, vel_d, oq, q_d, c->stream);
+			HIP_TRY(hipGetLastError());
+		} else {
+			Timed t(c, "pack_vtk_strided", pack_strided_traffic(c->geo, np, step, planes, (double)(vel_bytes + q_bytes)),
+			        c->stream);
+			launch_pack_vtk_strided(c->cur, c->geo, bmin, np, step, vel_d, oq, q_d, c->stream);
+			HIP_TRY(hipGetLastError());
+		}
 	}
-	if ((s = wait_stream(c, c->stream, "gcmx_snapshot_box")) != GCMX_OK) return s;
+	if ((s = wait_stream(c, c->stream, what)) != GCMX_OK) return s;
 	if (want_velocity && n_q > 0 && out == velocity + (size_t)n * 3) return observe_fetch(c, velocity, 0, vel_bytes + q_bytes);
 	if (want_velocity && (s = observe_fetch(c, velocity, 0, vel_bytes)) != GCMX_OK) return s;
 	if (n_q > 0 && (s = observe_fetch(c, out, vel_bytes, q_bytes)) != GCMX_OK) return s;
 	return GCMX_OK;
+}
+
+}  // namespace
+
+gcmx_status gcmx_snapshot_box(gcmx_ctx* c, const int bmin[3], const int bmax[3], int want_velocity, int n_q,
+                              const int* qs, float* velocity, float* out) {
+	return snapshot_impl(c, bmin, bmax, nullptr, want_velocity, n_q, qs, velocity, out, "gcmx_snapshot_box");
+}
+
+gcmx_status gcmx_snapshot_strided(gcmx_ctx* c, const int bmin[3], const int bmax[3], const int stride[3],
+                                  int want_velocity, int n_q, const int* qs, float* velocity, float* out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!stride) return fail(GCMX_ERR_INVALID_ARG, "null stride");
+	return snapshot_impl(c, bmin, bmax, stride, want_velocity, n_q, qs, velocity, out, "gcmx_snapshot_strided");
 }
 
 gcmx_status gcmx_scan(gcmx_ctx* c, gcmx_scan_result* out) {

@@ -5,6 +5,7 @@
 #include "observe.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace gcmx {
 
@@ -43,6 +44,12 @@ __global__ __launch_bounds__(256) void k_gather_q(const double* __restrict__ cur
 
 // The box of k_pack_vtk on the axes A (x: the VTK order's fastest), B (3-D: y) and
 // F (the layer's fastest: z in 3-D, y in 2-D, stride 1).
+// A strided launch (every stride-th node per axis) describes its lattice of
+// output points with the same fields: na, nb, nf count output points, sa and sb
+// are the element steps between selected rows (stride_a * Geo's, stride_b *
+// Geo's), a0 = b0 = 0 with the box minimum of A and B folded into the kernel's
+// `origin`, and f0 stays the first selected node of F; the step along F is the
+// kernel's `xf`.
 struct PackBox {
 	int a0, b0, f0;    // box minimum (inner indices)
 	int na, nb, nf;    // extents (nb = 1 below 3-D)
@@ -105,10 +112,22 @@ __device__ __forceinline__ void pack_load_tile(float* __restrict__ tile, const d
 // nearest even) happens before the LDS store.  Stores: a wave writes one (B, F)
 // line of the output, 64 consecutive points (256 B per quantity, 768 B of
 // Velocity as three instructions of 64 consecutive floats).
+// STRIDED: the box is a lattice (PackBox) whose output column f is node f0 + f * xf
+// of F, the layer's contiguous axis; only the load side's addressing differs.
+// Lane l of a tile row's load reads column f_base + l, that is 8 bytes every xf
+// elements: one instruction per row that touches 4 * xf lines of 128 B (64 at
+// most), every one of them a line the lattice needs.  Whole-line loads with
+// selection (xf coalesced 512-byte loads per row, a lane keeping the elements
+// with f = f0 mod xf) fetch the same lines and measured the same within the
+// spread at xf = 2, 4 and 8, so the simpler form is the one
+// kept.  Rows and columns past the tile's edge are clamped in output indices, so
+// a clamped load reads the last selected row or column, never a node outside the
+// box.  The unit-stride instance ignores xf.
+template <bool STRIDED>
 __global__ __launch_bounds__(256) void k_pack_vtk(const double* __restrict__ cur, long long cs,
                                                   long long origin, int D, PackBox bx,
                                                   float* __restrict__ vel, ObserveQ oq,
-                                                  float* __restrict__ qout) {
+                                                  float* __restrict__ qout, int xf) {
 	__shared__ float tile[3 * kTileSize];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	long long t = blockIdx.x;
@@ -121,8 +140,14 @@ __global__ __launch_bounds__(256) void k_pack_vtk(const double* __restrict__ cur
 	const long long n_total = (long long)bx.na * bx.nb * bx.nf;
 	// element offset of (a_base, b, f_base + lane); a lane past the tile's last column
 	// reads that column again (a load without a branch; the stores never read it)
-	const long long base = origin + (long long)(bx.a0 + a_base) * bx.sa + (long long)(bx.b0 + b) * bx.sb +
-	                       (bx.f0 + f_base + min(lane, height - 1));
+	long long base;
+	if constexpr (STRIDED) {
+		base = origin + (long long)a_base * bx.sa + (long long)b * bx.sb +
+		       (bx.f0 + (long long)(f_base + min(lane, height - 1)) * xf);
+	} else {
+		base = origin + (long long)(bx.a0 + a_base) * bx.sa + (long long)(bx.b0 + b) * bx.sb +
+		       (bx.f0 + f_base + min(lane, height - 1));
+	}
 	// first output point of line j of the tile: ((f * nb + b) * na + a_base)
 	const long long line0 = ((long long)f_base * bx.nb + b) * bx.na + a_base;
 	const long long line_step = (long long)bx.nb * bx.na;
@@ -156,13 +181,14 @@ __global__ __launch_bounds__(256) void k_pack_vtk(const double* __restrict__ cur
 	}
 }
 
-// 1-D: the layer's order is the VTK order; one thread per point.
+// 1-D: the layer's order is the VTK order; one thread per output point (node
+// a0 + i * xa).
 __global__ __launch_bounds__(256) void k_pack_line(const double* __restrict__ cur, long long cs, long long origin,
-                                                   int a0, int na, float* __restrict__ vel, ObserveQ oq,
+                                                   int a0, int na, int xa, float* __restrict__ vel, ObserveQ oq,
                                                    float* __restrict__ qout) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= na) return;
-	const long long off = origin + a0 + i;
+	const long long off = origin + a0 + (long long)i * xa;
 	if (vel) {
 		vel[3 * (long long)i] = (float)cur[off];
 		vel[3 * (long long)i + 1] = 0.0f;
@@ -240,7 +266,7 @@ void launch_pack_vtk(const double* cur, const Geo& g, const int bmin[3], const i
 	if (g.D == 1) {
 		const int na = bmax[0] - bmin[0];
 		hipLaunchKernelGGL(k_pack_line, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, cur, g.cs, g.origin,
-		                   bmin[0], na, vel_d, oq, q_d);
+		                   bmin[0], na, 1, vel_d, oq, q_d);
 		return;
 	}
 	const int F = g.D - 1;
@@ -256,8 +282,39 @@ void launch_pack_vtk(const double* cur, const Geo& g, const int bmin[3], const i
 	bx.ta = (bx.na + kTile - 1) / kTile;
 	bx.tf = (bx.nf + kTile - 1) / kTile;
 	const long long blocks = (long long)bx.ta * bx.tf * bx.nb;
-	hipLaunchKernelGGL(k_pack_vtk, dim3((unsigned)blocks), dim3(256), 0, st, cur, g.cs, g.origin, g.D, bx, vel_d, oq,
-	                   q_d);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_vtk<false>), dim3((unsigned)blocks), dim3(256), 0, st, cur, g.cs,
+	                   g.origin, g.D, bx, vel_d, oq, q_d, 1);
+}
+
+void launch_pack_vtk_strided(const double* cur, const Geo& g, const int bmin[3], const int n[3], const int step[3],
+                             float* vel_d, const ObserveQ& oq, float* q_d, hipStream_t st) {
+	if (g.D == 1) {
+		hipLaunchKernelGGL(k_pack_line, dim3((unsigned)((n[0] + 255) / 256)), dim3(256), 0, st, cur, g.cs, g.origin,
+		                   bmin[0], n[0], step[0], vel_d, oq, q_d);
+		return;
+	}
+	const int F = g.D - 1;
+	PackBox bx;
+	bx.a0 = bx.b0 = 0;
+	bx.na = n[0];
+	bx.nb = g.D == 3 ? n[1] : 1;
+	bx.f0 = bmin[F];
+	bx.nf = n[F];
+	bx.sa = (long long)step[0] * g.stride[0];
+	bx.sb = g.D == 3 ? (long long)step[1] * g.stride[1] : 0;
+	bx.ta = (bx.na + kTile - 1) / kTile;
+	bx.tf = (bx.nf + kTile - 1) / kTile;
+	const long long origin = g.origin + (long long)bmin[0] * g.stride[0] + (g.D == 3 ? (long long)bmin[1] * g.stride[1] : 0);
+	const long long blocks = (long long)bx.ta * bx.tf * bx.nb;
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_vtk<true>), dim3((unsigned)blocks), dim3(256), 0, st, cur, g.cs, origin,
+	                   g.D, bx, vel_d, oq, q_d, step[F]);
+}
+
+double pack_strided_traffic(const Geo& g, const int n[3], const int step[3], double planes, double out_bytes) {
+	const int F = g.D - 1;
+	const double rows = g.D == 1 ? 1.0 : (double)n[0] * (g.D == 3 ? n[1] : 1);
+	const double span_lines = std::ceil((((double)n[F] - 1) * step[F] + 1) * sizeof(double) / 128.0);
+	return rows * planes * std::min(span_lines, (double)n[F]) * 128.0 + out_bytes;
 }
 
 void launch_scan(const double* cur, const Geo& g, unsigned long long* res_d, hipStream_t st) {

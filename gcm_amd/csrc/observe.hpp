@@ -2,7 +2,8 @@
 // what a snapshotter or a detector needs from the current layer, formed on the
 // device so that no call moves a whole layer to the host.
 //   k_gather_q  quantities at listed nodes                 (gcmx_gather)
-//   k_pack_vtk  the Float32 arrays of a box, VTK order     (gcmx_snapshot_box)
+//   k_pack_vtk  the Float32 arrays of a box, VTK order     (gcmx_snapshot_box;
+//               every k-th node per axis: gcmx_snapshot_strided)
 //   k_scan      non-finite count and max |v| per component (gcmx_scan)
 // Quantities are getQuantityOf's (host/task.hpp:134-143, host/acoustic_model.hpp:
 // 145-180), bitwise: a component itself, or the elastic PRESSURE
@@ -33,6 +34,20 @@ void launch_gather_q(const double* cur, const Geo& g, long long n, const long lo
 // axis is the VTK order's slowest); 1-D copies.
 void launch_pack_vtk(const double* cur, const Geo& g, const int bmin[3], const int bmax[3],
                      float* vel_d, const ObserveQ& oq, float* q_d, hipStream_t st);
+
+// The same arrays over the lattice of every step[d]-th inner node from bmin: n[d]
+// output points along axis d, point i_d is node bmin[d] + i_d * step[d] (the
+// caller keeps the last one inside the inner box).  The STRIDED instance of
+// k_pack_vtk: selected rows only along A and B; along F, the layer's contiguous
+// axis, lane-strided 8-byte loads.  1-D: k_pack_line with the
+// stride.
+void launch_pack_vtk_strided(const double* cur, const Geo& g, const int bmin[3], const int n[3], const int step[3],
+                             float* vel_d, const ObserveQ& oq, float* q_d, hipStream_t st);
+// The compulsory traffic of that launch: HBM delivers whole 128-byte lines, so
+// per selected row and fp64 plane read (`planes` per output point: Velocity's D, a
+// trace's D, else 1) min(lines of the row's span, output points of the row) lines,
+// plus the Float32 bytes written.
+double pack_strided_traffic(const Geo& g, const int n[3], const int step[3], double planes, double out_bytes);
 
 // res_d[0] = number of non-finite component values over the inner nodes (64-bit),
 // res_d[1 + c] = bits of max |v| over the finite values of component c (0.0 when

@@ -49,7 +49,7 @@ SYMBOLS = [
     "gcmx_create", "gcmx_create_model", "gcmx_get_model", "gcmx_destroy", "gcmx_set_materials", "gcmx_matrix_structure", "gcmx_set_material_ids",
     "gcmx_upload", "gcmx_download", "gcmx_read_box", "gcmx_write_box", "gcmx_fill_random",
     "gcmx_setup_state", "gcmx_setup_census", "gcmx_setup_material_ids", "gcmx_download_material_ids",
-    "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_scan",
+    "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_snapshot_strided", "gcmx_scan",
     "gcmx_transfer_stats",
     "gcmx_stage", "gcmx_step",
     "gcmx_set_kernel_path", "gcmx_set_step_schedule", "gcmx_set_fp_mode", "gcmx_get_fp_mode", "gcmx_effective_path", "gcmx_last_step_path",
@@ -208,6 +208,9 @@ def lib() -> ctypes.CDLL:
         L.gcmx_gather.argtypes = [vp, vp, ctypes.c_int, ip, dp]
         L.gcmx_snapshot_box.argtypes = [vp, ip, ip, ctypes.c_int, ctypes.c_int, ip, fp, fp]
         L.gcmx_scan.argtypes = [vp, ctypes.POINTER(ScanResult)]
+    if hasattr(L, "gcmx_snapshot_strided"):
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.gcmx_snapshot_strided.argtypes = [vp, ip, ip, ip, ctypes.c_int, ctypes.c_int, ip, fp, fp]
         L.gcmx_transfer_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.gcmx_stage.argtypes = [vp, ctypes.c_int, ctypes.c_double]
     L.gcmx_step.argtypes = [vp, ctypes.c_double]
@@ -502,6 +505,24 @@ class Context:
         _check(lib().gcmx_snapshot_box(self._ptr, _ip(lo), _ip(hi), 1 if velocity else 0, len(quantities),
                                        _ip(quantities), vel.ctypes.data_as(fp) if velocity else None,
                                        q.ctypes.data_as(fp) if len(quantities) else None))
+        return vel, q
+
+    def snapshot_strided(self, box_min: Sequence[int], box_max: Sequence[int], stride: Sequence[int],
+                         quantities: Sequence[int], velocity: bool = True):
+        """gcmx_snapshot_strided: snapshot_box at every stride[d]-th node of the box,
+        ceil(extent / stride) points per axis from box_min.  Returns (velocity
+        [n, 3] or None, values [n_q, n]) over that lattice, VTK point order."""
+        pad = lambda v, fill: list(v)[:self.dim] + [fill] * (3 - self.dim)
+        lo, hi, st = pad(box_min, 0), pad(box_max, 1), pad(stride, 1)
+        n = int(np.prod([max(0, -(-(b - a) // s)) if s > 0 else 0 for a, b, s in zip(lo, hi, st)]))
+        fp = ctypes.POINTER(ctypes.c_float)
+        buf = np.empty(max(1, n * ((3 if velocity else 0) + len(quantities))), dtype=np.float32)
+        vel = buf[:3 * n].reshape(n, 3) if velocity else None
+        q = buf[(3 * n if velocity else 0):][:n * len(quantities)].reshape(len(quantities), n)
+        _check(lib().gcmx_snapshot_strided(self._ptr, _ip(lo), _ip(hi), _ip(st), 1 if velocity else 0,
+                                           len(quantities), _ip(quantities),
+                                           vel.ctypes.data_as(fp) if velocity else None,
+                                           q.ctypes.data_as(fp) if len(quantities) else None))
         return vel, q
 
     def scan(self):

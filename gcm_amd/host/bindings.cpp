@@ -200,10 +200,14 @@ py::dict hostState(const Task& task, size_t id) {
 }
 
 /// VtkSnapshotter's file for body `id` without a GPU: the set-up layer of the
-/// task, or `pde` (all nodes incl. ghosts, [..., M]) when given.
+/// task, or `pde` (all nodes incl. ghosts, [..., M]) when given.  The task's vtk
+/// stride and box select the nodes as in the engine; false (and no file): the box
+/// misses the body.
 template <int D>
-void writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::object pde) {
+bool writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::object pde) {
 	cubic::CubicGrid<D> grid(id, cubic::constructionPack<D>(task, id));
+	cubic::VtkSelection<D> sel;
+	if (!cubic::vtkSelectionOf<D>(task.vtkSnapshotter, grid.sizes, grid.start, sel)) return false;
 	auto st = cubic::buildHostState<D>(task, grid);
 	std::vector<real> layer = st.pde;
 	if (!pde.is_none()) {
@@ -214,7 +218,8 @@ void writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::
 	makeParentDirectories(fileName);
 	cubic::writeVtkSnapshot<D>(fileName, grid.sizes, grid.start, grid.h, grid.borderSize,
 	                           layer.data(), st.matId.data(), st.materialNumber,
-	                           task.vtkSnapshotter.quantitiesToSnap, st.model);
+	                           task.vtkSnapshotter.quantitiesToSnap, st.model, sel);
+	return true;
 }
 
 /// The array loop of the GPU-free VtkSnapshotter alone (cubic::vtkLayerArrays): the
@@ -222,7 +227,8 @@ void writeVtkHost(const Task& task, size_t id, const std::string& fileName, py::
 /// all-nodes order, as numpy arrays that own the vectors (no copy).
 template <int D>
 py::dict vtkLayerArraysHost(const std::vector<int>& sizes, int borderSize, py::array_t<real, py::array::c_style> pde,
-                            const std::vector<std::string>& quantities, bool acoustic) {
+                            const std::vector<std::string>& quantities, bool acoustic, const std::vector<int>& boxMin,
+                            const std::vector<int>& boxMax, const std::vector<int>& stride) {
 	std::array<int, D> sz;
 	size_t all = 1;
 	for (int i = 0; i < D; i++) {
@@ -235,7 +241,14 @@ py::dict vtkLayerArraysHost(const std::vector<int>& sizes, int borderSize, py::a
 	for (const auto& q : quantities) qs.push_back(quantity(q));
 	cubic::VtsArray vel;
 	std::vector<cubic::VtsArray> arrays;
-	cubic::vtkLayerArrays<D>(sz, borderSize, pde.data(), qs, model, vel, arrays);
+	// the selection: an empty list is the whole body / every node
+	cubic::VtkSelection<D> sel;
+	for (int i = 0; i < D; i++) {
+		sel.lo[i] = boxMin.empty() ? 0 : boxMin.at((size_t)i);
+		sel.hi[i] = boxMax.empty() ? sz[i] : boxMax.at((size_t)i);
+		sel.stride[i] = stride.empty() ? 1 : stride.at((size_t)i);
+	}
+	cubic::vtkLayerArrays<D>(sz, borderSize, pde.data(), qs, model, sel, vel, arrays);
 	auto adopt = [](std::vector<float>&& v, std::vector<ssize_t> shape) {
 		auto* heap = new std::vector<float>(std::move(v));
 		py::capsule owner(heap, [](void* p) { delete static_cast<std::vector<float>*>(p); });
@@ -458,6 +471,30 @@ PYBIND11_MODULE(_gcm_host, m) {
 	         })
 	    .def("set_vtk_chunk_bytes", [](Task& t, size_t bytes) { t.vtkSnapshotter.chunkBytes = bytes; },
 	         "most output bytes one device request of the cubic VtkSnapshotter carries (default 256 MiB)")
+	    .def("set_vtk_stride",
+	         [](Task& t, const std::vector<int>& stride) {
+		         if (stride.empty() || stride.size() > 3) throw Exception("set_vtk_stride: one stride per axis");
+		         t.vtkSnapshotter.stride = {1, 1, 1};
+		         for (size_t i = 0; i < stride.size(); i++) {
+			         if (stride[i] < 1) throw Exception("set_vtk_stride: a stride is at least 1");
+			         t.vtkSnapshotter.stride[i] = stride[i];
+		         }
+	         },
+	         "the cubic VtkSnapshotter writes every stride[d]-th node along axis d (default: every node)")
+	    .def("set_vtk_box",
+	         [](Task& t, const std::vector<int>& lo, const std::vector<int>& hi) {
+		         if (lo.empty() || lo.size() > 3 || hi.size() != lo.size()) throw Exception("set_vtk_box: one index per axis");
+		         t.vtkSnapshotter.hasBox = true;
+		         t.vtkSnapshotter.boxMin = {0, 0, 0};
+		         t.vtkSnapshotter.boxMax = {1, 1, 1};
+		         for (size_t i = 0; i < lo.size(); i++) {
+			         t.vtkSnapshotter.boxMin[i] = lo[i];
+			         t.vtkSnapshotter.boxMax[i] = hi[i];
+		         }
+	         },
+	         py::arg("lo"), py::arg("hi"),
+	         "the cubic VtkSnapshotter writes the inner nodes [lo, hi) only (global node indices, clipped to each "
+	         "body; a body the box misses writes no file)")
 	    .def("set_checkpoint",
 	         [](Task& t, const std::string& directory, int steps) {
 		         t.checkpoint.directory = directory;
@@ -619,22 +656,28 @@ PYBIND11_MODULE(_gcm_host, m) {
 		    if (D == 3) return writeVtkHost<3>(t, id, fileName, pde);
 		    throw Exception("dimensionality must be 1, 2 or 3");
 	    },
-	    "GPU-free VtkSnapshotter file of one body (set-up layer, or `pde`)", py::arg("task"),
+	    "GPU-free VtkSnapshotter file of one body (set-up layer, or `pde`) with the task's vtk stride and box; "
+	    "False: the box misses the body, no file",
+	    py::arg("task"),
 	    py::arg("body_id"), py::arg("file_name"), py::arg("pde") = py::none());
 
 	m.def(
 	    "vtk_layer_arrays",
 	    [](const std::vector<int>& sizes, int borderSize, py::array_t<real, py::array::c_style> pde,
-	       const std::vector<std::string>& quantities, const std::string& model) {
+	       const std::vector<std::string>& quantities, const std::string& model, const std::vector<int>& boxMin,
+	       const std::vector<int>& boxMax, const std::vector<int>& stride) {
 		    if (model != "elastic" && model != "acoustic") throw Exception("model must be elastic or acoustic");
 		    const bool ac = model == "acoustic";
-		    if (sizes.size() == 1) return vtkLayerArraysHost<1>(sizes, borderSize, pde, quantities, ac);
-		    if (sizes.size() == 2) return vtkLayerArraysHost<2>(sizes, borderSize, pde, quantities, ac);
-		    if (sizes.size() == 3) return vtkLayerArraysHost<3>(sizes, borderSize, pde, quantities, ac);
+		    if (sizes.size() == 1) return vtkLayerArraysHost<1>(sizes, borderSize, pde, quantities, ac, boxMin, boxMax, stride);
+		    if (sizes.size() == 2) return vtkLayerArraysHost<2>(sizes, borderSize, pde, quantities, ac, boxMin, boxMax, stride);
+		    if (sizes.size() == 3) return vtkLayerArraysHost<3>(sizes, borderSize, pde, quantities, ac, boxMin, boxMax, stride);
 		    throw Exception("dimensionality must be 1, 2 or 3");
 	    },
-	    "GPU-free VtkSnapshotter array loop: Float32 Velocity and quantity arrays (VTK order) of an all-nodes layer",
-	    py::arg("sizes"), py::arg("border_size"), py::arg("pde"), py::arg("quantities"), py::arg("model") = "elastic");
+	    "GPU-free VtkSnapshotter array loop: Float32 Velocity and quantity arrays (VTK order) of an all-nodes layer, "
+	    "or of every stride[d]-th inner node of [box_min, box_max)",
+	    py::arg("sizes"), py::arg("border_size"), py::arg("pde"), py::arg("quantities"), py::arg("model") = "elastic",
+	    py::arg("box_min") = std::vector<int>{}, py::arg("box_max") = std::vector<int>{},
+	    py::arg("stride") = std::vector<int>{});
 
 	m.def(
 	    "write_simplex_vtk",

@@ -801,6 +801,22 @@ void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const st
 }
 
 template <int D>
+void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const IntD& stride,
+                                const std::vector<int>& quantities, float* velocity, float* values) const {
+	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1}, st[3] = {1, 1, 1};
+	for (int d = 0; d < D; d++) {
+		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("snapshotArrays: only inner nodes can be observed");
+		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
+		lo[d] = boxMin[d] + off;
+		hi[d] = boxMax[d] + off;
+		st[d] = stride[d];
+	}
+	gcmxCheck(gcmx_snapshot_strided(ctx_, lo, hi, st, velocity ? 1 : 0, (int)quantities.size(), quantities.data(),
+	                                velocity, values),
+	          "gcmx_snapshot_strided");
+}
+
+template <int D>
 std::array<uint64_t, 2> HipMesh<D>::transferBytes() const {
 	uint64_t v[2] = {0, 0};
 	gcmxCheck(gcmx_transfer_stats(ctx_, v), "gcmx_transfer_stats");
@@ -1392,8 +1408,9 @@ template <int D>
 void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) {
 	const HipMesh<D>* mesh = dynamic_cast<const HipMesh<D>*>(mesh_);
 	if (!mesh) throw Exception("VtkSnapshotter: not a cubic mesh");
-	size_t n = 1;
-	for (int i = 0; i < D; i++) n *= (size_t)mesh->sizes[i];
+	VtkSelection<D> sel;
+	if (!vtkSelectionOf<D>(settings, mesh->sizes, mesh->start, sel)) return;  // the box misses this body
+	const size_t n = sel.points();
 	VtsArray vel{"Velocity", 3, std::vector<float>(3 * n)};
 	std::vector<VtsArray> qs;
 	std::vector<int> codes;
@@ -1402,18 +1419,20 @@ void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) 
 		qs.push_back(VtsArray{quantityName(q), 1, std::vector<float>(n)});
 		codes.push_back(quantityCode(q));
 	}
-	// Slabs along the slowest VTK axis (the last one): whole lines and planes of the
-	// file's point order, so a slab's arrays are contiguous parts of the file's.
+	// Slabs along the slowest VTK axis (the last one), counted in output indices:
+	// whole lines and planes of the file's point order, so a slab's arrays are
+	// contiguous parts of the file's.
 	const int slow = D - 1;
-	const size_t plane = n / (size_t)mesh->sizes[slow];  // points per index of the slow axis
+	const size_t nSlow = (size_t)sel.points(slow);
+	const size_t plane = n / nSlow;  // points per index of the slow axis
 	const size_t perPoint = 4 * (3 + qs.size());
 	const size_t thick = std::max<size_t>(1, chunkBytes / (plane * perPoint));
 	std::vector<float> slab;  // [quantities][points of the slab], when there are several
-	for (size_t s0 = 0; s0 < (size_t)mesh->sizes[slow]; s0 += thick) {
-		const size_t s1 = std::min<size_t>(s0 + thick, (size_t)mesh->sizes[slow]);
-		std::array<int, D> lo{}, hi = mesh->sizes;
-		lo[slow] = (int)s0;
-		hi[slow] = (int)s1;
+	for (size_t s0 = 0; s0 < nSlow; s0 += thick) {
+		const size_t s1 = std::min<size_t>(s0 + thick, nSlow);
+		std::array<int, D> lo = sel.lo, hi = sel.hi;
+		lo[slow] = sel.lo[slow] + (int)s0 * sel.stride[slow];
+		hi[slow] = std::min(sel.hi[slow], sel.lo[slow] + (int)(s1 - 1) * sel.stride[slow] + 1);
 		const size_t first = s0 * plane, count = (s1 - s0) * plane;
 		float* values = nullptr;
 		if (qs.size() == 1) values = qs[0].values.data() + first;
@@ -1421,7 +1440,7 @@ void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) 
 			slab.resize(qs.size() * count);
 			values = slab.data();
 		}
-		mesh->snapshotArrays(lo, hi, codes, vel.values.data() + 3 * first, values);
+		mesh->snapshotArrays(lo, hi, sel.stride, codes, vel.values.data() + 3 * first, values);
 		if (qs.size() > 1)
 			for (size_t k = 0; k < qs.size(); k++)
 				std::copy(slab.begin() + k * count, slab.begin() + (k + 1) * count, qs[k].values.begin() + first);
@@ -1429,7 +1448,7 @@ void VtkSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) 
 	const auto& ids = mesh->materialIdsAll();
 	writeVtkArrays<D>(makeFileNameForSnapshot(std::to_string(mesh->id), step, "vts", "vtk"), mesh->sizes,
 	                  mesh->start, mesh->h, mesh->borderSize, ids.empty() ? nullptr : ids.data(),
-	                  mesh->materialNumbers(), std::move(vel), std::move(qs));
+	                  mesh->materialNumbers(), sel, std::move(vel), std::move(qs));
 }
 
 template <int D>

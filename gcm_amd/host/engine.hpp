@@ -230,6 +230,10 @@ public:
 	/// fastest): velocity[n][3] (null: not wanted) and values[quantities][n].
 	void snapshotArrays(const IntD& boxMin, const IntD& boxMax, const std::vector<int>& quantities,
 	                    float* velocity, float* values) const;
+	/// The same at every stride[d]-th node of the box (gcmx_snapshot_strided):
+	/// ceil(extent / stride) points per axis, counted from boxMin.
+	void snapshotArrays(const IntD& boxMin, const IntD& boxMax, const IntD& stride, const std::vector<int>& quantities,
+	                    float* velocity, float* values) const;
 	/// Bytes the body's context copied {device -> host, host -> device} (gcmx_transfer_stats).
 	std::array<uint64_t, 2> transferBytes() const;
 	int numberOfMaterials() const { return (int)(model_ == Models::T::ACOUSTIC ? acousticMatrices.size() : matrices.size()); }
@@ -404,17 +408,20 @@ class VtkSnapshotter : public Snapshotter {
 public:
 	explicit VtkSnapshotter(const Task& task)
 	    : Snapshotter(task), quantitiesToSnap(task.vtkSnapshotter.quantitiesToSnap),
-	      chunkBytes(task.vtkSnapshotter.chunkBytes) {}
+	      chunkBytes(task.vtkSnapshotter.chunkBytes), settings(task.vtkSnapshotter) {}
 
 protected:
 	/// The file's Velocity and quantity arrays come from the device already as
 	/// Float32 in VTK order (HipMesh::snapshotArrays), in slabs along the slowest VTK
-	/// axis of at most chunkBytes of output each.
+	/// axis of at most chunkBytes of output each.  With Task::vtkSnapshotter.stride
+	/// or .box the file holds the selected nodes only (VtkSelection), the slabs are
+	/// counted in output indices, and a body the box misses writes no file.
 	void snapshotImpl(const AbstractGrid* mesh, const int step) override;
 
 private:
 	const std::vector<PhysicalQuantities::T> quantitiesToSnap;
 	const size_t chunkBytes;
+	const Task::VtkSnapshotter settings;
 };
 
 /// SliceSnapshotter<Mesh> (util/snapshot/SliceSnapshotter.hpp:12-118): velocity

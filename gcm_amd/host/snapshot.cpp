@@ -5,6 +5,7 @@
 
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <fstream>
@@ -216,12 +217,53 @@ static void indexMakerOf(const std::array<int, D>& sizes, int borderSize, long l
 }
 
 template <int D>
+static VtkSelection<D> wholeBody(const std::array<int, D>& sizes) {
+	VtkSelection<D> sel;
+	for (int i = 0; i < D; i++) {
+		sel.lo[i] = 0;
+		sel.hi[i] = sizes[i];
+		sel.stride[i] = 1;
+	}
+	return sel;
+}
+
+template <int D>
+static void checkSelection(const VtkSelection<D>& sel, const std::array<int, D>& sizes) {
+	for (int i = 0; i < D; i++) {
+		if (sel.stride[i] < 1) throw Exception("vtk selection: a stride is at least 1");
+		if (sel.lo[i] < 0 || sel.hi[i] > sizes[i] || sel.hi[i] <= sel.lo[i])
+			throw Exception("vtk selection: an empty box or one outside the inner nodes");
+	}
+}
+
+template <int D>
+bool vtkSelectionOf(const Task::VtkSnapshotter& settings, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, VtkSelection<D>& sel) {
+	sel = wholeBody<D>(sizes);
+	for (int i = 0; i < D; i++) {
+		if (settings.stride[i] < 1) throw Exception("vtkSnapshotter.stride: a stride is at least 1");
+		sel.stride[i] = settings.stride[i];
+		if (!settings.hasBox) continue;
+		// long long: a box may be given as "everything" with the largest ints
+		sel.lo[i] = (int)std::max<long long>(0, (long long)settings.boxMin[i] - start[i]);
+		sel.hi[i] = (int)std::min<long long>(sizes[i], (long long)settings.boxMax[i] - start[i]);
+		if (sel.hi[i] <= sel.lo[i]) return false;
+	}
+	return true;
+}
+
+template <int D>
 void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real* pdeAll,
-                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model, VtsArray& vel,
-                    std::vector<VtsArray>& qs) {
+                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model,
+                    const VtkSelection<D>& sel, VtsArray& vel, std::vector<VtsArray>& qs) {
+	checkSelection<D>(sel, sizes);
 	const int M = pdeSizeOf(model, D);
-	int dims[3] = {1, 1, 1};
-	for (int i = 0; i < D; i++) dims[i] = sizes[i];
+	int dims[3] = {1, 1, 1}, lo[3] = {0, 0, 0}, step[3] = {1, 1, 1};
+	for (int i = 0; i < D; i++) {
+		dims[i] = sel.points(i);
+		lo[i] = sel.lo[i];
+		step[i] = sel.stride[i];
+	}
 	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
 	long long im[3];
 	indexMakerOf<D>(sizes, borderSize, im);
@@ -236,7 +278,7 @@ void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real*
 	for (int z = 0; z < dims[2]; z++)
 		for (int y = 0; y < dims[1]; y++)
 			for (int x = 0; x < dims[0]; x++, p++) {
-				const int it[3] = {x, y, z};
+				const int it[3] = {lo[0] + x * step[0], lo[1] + y * step[1], lo[2] + z * step[2]};
 				long long idx = 0;
 				for (int i = 0; i < D; i++) idx += im[i] * (it[i] + borderSize);
 				const real* v = pdeAll + (size_t)idx * M;
@@ -249,10 +291,15 @@ void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real*
 template <int D>
 void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes,
                     const std::array<int, D>& start, const std::array<real, D>& h, int borderSize,
-                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers, VtsArray vel,
-                    std::vector<VtsArray> qs) {
-	int dims[3] = {1, 1, 1};
-	for (int i = 0; i < D; i++) dims[i] = sizes[i];
+                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers,
+                    const VtkSelection<D>& sel, VtsArray vel, std::vector<VtsArray> qs) {
+	checkSelection<D>(sel, sizes);
+	int dims[3] = {1, 1, 1}, lo[3] = {0, 0, 0}, step[3] = {1, 1, 1};
+	for (int i = 0; i < D; i++) {
+		dims[i] = sel.points(i);
+		lo[i] = sel.lo[i];
+		step[i] = sel.stride[i];
+	}
 	const size_t n = (size_t)dims[0] * dims[1] * dims[2];
 	long long im[3];
 	indexMakerOf<D>(sizes, borderSize, im);
@@ -262,7 +309,7 @@ void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes
 	for (int z = 0; z < dims[2]; z++)
 		for (int y = 0; y < dims[1]; y++)
 			for (int x = 0; x < dims[0]; x++, p++) {
-				const int it[3] = {x, y, z};
+				const int it[3] = {lo[0] + x * step[0], lo[1] + y * step[1], lo[2] + z * step[2]};
 				long long idx = 0;
 				for (int i = 0; i < D; i++) idx += im[i] * (it[i] + borderSize);
 				for (int i = 0; i < 3; i++) {
@@ -284,12 +331,40 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
                       const std::array<int, D>& start, const std::array<real, D>& h,
                       int borderSize, const real* pdeAll, const uint8_t* matIdAll,
                       const std::vector<int>& materialNumbers,
-                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model) {
+                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model,
+                      const VtkSelection<D>& sel) {
 	VtsArray vel;
 	std::vector<VtsArray> qs;
-	vtkLayerArrays<D>(sizes, borderSize, pdeAll, quantities, model, vel, qs);
-	writeVtkArrays<D>(fileName, sizes, start, h, borderSize, matIdAll, materialNumbers, std::move(vel),
+	vtkLayerArrays<D>(sizes, borderSize, pdeAll, quantities, model, sel, vel, qs);
+	writeVtkArrays<D>(fileName, sizes, start, h, borderSize, matIdAll, materialNumbers, sel, std::move(vel),
 	                  std::move(qs));
+}
+
+// The whole body, every node: the selection that is all of it.
+template <int D>
+void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real* pdeAll,
+                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model, VtsArray& vel,
+                    std::vector<VtsArray>& qs) {
+	vtkLayerArrays<D>(sizes, borderSize, pdeAll, quantities, model, wholeBody<D>(sizes), vel, qs);
+}
+
+template <int D>
+void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, const std::array<real, D>& h, int borderSize,
+                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers, VtsArray vel,
+                    std::vector<VtsArray> qs) {
+	writeVtkArrays<D>(fileName, sizes, start, h, borderSize, matIdAll, materialNumbers, wholeBody<D>(sizes),
+	                  std::move(vel), std::move(qs));
+}
+
+template <int D>
+void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& sizes,
+                      const std::array<int, D>& start, const std::array<real, D>& h,
+                      int borderSize, const real* pdeAll, const uint8_t* matIdAll,
+                      const std::vector<int>& materialNumbers,
+                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model) {
+	writeVtkSnapshot<D>(fileName, sizes, start, h, borderSize, pdeAll, matIdAll, materialNumbers, quantities, model,
+	                    wholeBody<D>(sizes));
 }
 
 #define GCM_SNAPSHOT_INSTANCES(D)                                                                             \
@@ -302,7 +377,20 @@ void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& siz
 	template void writeVtkSnapshot<D>(const std::string&, const std::array<int, D>&,                          \
 	                                  const std::array<int, D>&, const std::array<real, D>&, int,             \
 	                                  const real*, const uint8_t*, const std::vector<int>&,                   \
-	                                  const std::vector<PhysicalQuantities::T>&, Models::T);
+	                                  const std::vector<PhysicalQuantities::T>&, Models::T);                  \
+	template bool vtkSelectionOf<D>(const Task::VtkSnapshotter&, const std::array<int, D>&,                   \
+	                                const std::array<int, D>&, VtkSelection<D>&);                             \
+	template void vtkLayerArrays<D>(const std::array<int, D>&, int, const real*,                              \
+	                                const std::vector<PhysicalQuantities::T>&, Models::T,                     \
+	                                const VtkSelection<D>&, VtsArray&, std::vector<VtsArray>&);               \
+	template void writeVtkArrays<D>(const std::string&, const std::array<int, D>&, const std::array<int, D>&, \
+	                                const std::array<real, D>&, int, const uint8_t*, const std::vector<int>&, \
+	                                const VtkSelection<D>&, VtsArray, std::vector<VtsArray>);                 \
+	template void writeVtkSnapshot<D>(const std::string&, const std::array<int, D>&,                          \
+	                                  const std::array<int, D>&, const std::array<real, D>&, int,             \
+	                                  const real*, const uint8_t*, const std::vector<int>&,                   \
+	                                  const std::vector<PhysicalQuantities::T>&, Models::T,                   \
+	                                  const VtkSelection<D>&);
 GCM_SNAPSHOT_INSTANCES(1)
 GCM_SNAPSHOT_INSTANCES(2)
 GCM_SNAPSHOT_INSTANCES(3)

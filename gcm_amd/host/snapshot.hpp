@@ -139,6 +139,47 @@ void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes
                     const uint8_t* matIdAll, const std::vector<int>& materialNumbers, VtsArray velocity,
                     std::vector<VtsArray> quantityArrays);
 
+/// A SELECTION of a body's inner nodes (Task::vtkSnapshotter.box / .stride): along
+/// axis d the nodes lo[d] + i * stride[d] < hi[d], points(d) of them.  The file of
+/// a selection holds those nodes only: extents 0 ... points(d) - 1, "Points" the
+/// nodes' own coordinates, "material_index" their ids.
+template <int D>
+struct VtkSelection {
+	std::array<int, D> lo, hi, stride;
+	int points(int d) const { return (int)(((long long)hi[d] - lo[d] + stride[d] - 1) / stride[d]); }
+	size_t points() const {
+		size_t n = 1;
+		for (int d = 0; d < D; d++) n *= (size_t)points(d);
+		return n;
+	}
+};
+/// The selection of the body (sizes, start) a task asks for: the whole body at
+/// the task's stride, or the task's box (global node indices) clipped to the
+/// body, the stride counted from the clipped minimum.  False: the box misses the
+/// body, which then writes no file.
+template <int D>
+bool vtkSelectionOf(const Task::VtkSnapshotter& settings, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, VtkSelection<D>& selection);
+/// The overloads of the three writers above for a selection; the whole body at
+/// stride 1 gives the files and arrays of the ones above byte for byte.  No array
+/// of the body's size is built.
+template <int D>
+void vtkLayerArrays(const std::array<int, D>& sizes, int borderSize, const real* pdeAll,
+                    const std::vector<PhysicalQuantities::T>& quantities, Models::T model,
+                    const VtkSelection<D>& selection, VtsArray& velocity, std::vector<VtsArray>& quantityArrays);
+template <int D>
+void writeVtkArrays(const std::string& fileName, const std::array<int, D>& sizes,
+                    const std::array<int, D>& start, const std::array<real, D>& h, int borderSize,
+                    const uint8_t* matIdAll, const std::vector<int>& materialNumbers,
+                    const VtkSelection<D>& selection, VtsArray velocity, std::vector<VtsArray> quantityArrays);
+template <int D>
+void writeVtkSnapshot(const std::string& fileName, const std::array<int, D>& sizes,
+                      const std::array<int, D>& start, const std::array<real, D>& h,
+                      int borderSize, const real* pdeAll, const uint8_t* matIdAll,
+                      const std::vector<int>& materialNumbers,
+                      const std::vector<PhysicalQuantities::T>& quantities, Models::T model,
+                      const VtkSelection<D>& selection);
+
 const char* quantityName(PhysicalQuantities::T q);
 
 }  // namespace cubic

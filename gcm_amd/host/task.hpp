@@ -316,6 +316,15 @@ struct Task {
 		/// Host only: most output bytes one device -> host request of the cubic
 		/// VtkSnapshotter carries (it asks for the box in slabs of at most this).
 		size_t chunkBytes = 256u << 20;
+		/// Host only: the cubic VtkSnapshotter writes every stride[d]-th node along
+		/// axis d (picked, not averaged) ...
+		std::array<int, 3> stride = {1, 1, 1};
+		/// ... of the inner nodes [boxMin, boxMax), given as global node indices (a
+		/// body's `start` counts in them) and clipped to each body; the stride counts
+		/// from the clipped minimum.  A body the box misses writes no file for that
+		/// snapshot.  Without a box: the whole body.
+		bool hasBox = false;
+		std::array<int, 3> boxMin = {0, 0, 0}, boxMax = {0, 0, 0};
 	} vtkSnapshotter;
 
 	/// Host only: run() of the cubic engine saves its state (Engine::saveState) after

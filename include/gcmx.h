@@ -305,6 +305,18 @@ gcmx_status gcmx_gather(gcmx_ctx* ctx, const gcmx_node_list* list, int n_q, cons
  * copy (one copy for both when `out` follows `velocity` directly). */
 gcmx_status gcmx_snapshot_box(gcmx_ctx* ctx, const int box_min[3], const int box_max[3], int want_velocity,
                               int n_q, const int* quantities, float* velocity, float* out);
+/* gcmx_snapshot_box at every stride[d]-th node of the box: along axis d the call
+ * takes n_d = ceil((box_max[d] - box_min[d]) / stride[d]) points, point i_d being
+ * inner node box_min[d] + i_d * stride[d] (entries >= dim are ignored, n_d = 1
+ * there).  Layout, quantities, values and copies are gcmx_snapshot_box's over the
+ * n_0 x n_1 x n_2 lattice, n = n_0 n_1 n_2; with stride {1, 1, 1} the result is
+ * gcmx_snapshot_box's bit for bit.  A stride is >= 1; one larger than the extent
+ * gives one point on that axis.  A null stride, a stride <= 0 and every refusal
+ * of gcmx_snapshot_box are GCMX_ERR_INVALID_ARG and change nothing.  The points
+ * are picked, not averaged. */
+gcmx_status gcmx_snapshot_strided(gcmx_ctx* ctx, const int box_min[3], const int box_max[3],
+                                  const int stride[3], int want_velocity, int n_q,
+                                  const int* quantities, float* velocity, float* out);
 /* Health check of the current layer's inner nodes: the number of non-finite
  * component values, and per component the maximum of |v| over the finite values
  * (0.0 when there is none; entries >= M are 0.0).  Deterministic. */
