@@ -194,106 +194,6 @@ void HipMesh<D>::joinStack(const std::shared_ptr<HipMesh<D>>& stack, int axis, i
 	stackOffset_ = offset;
 }
 
-template <int D>
-HostState<D> HipMesh<D>::setUpMember(const Task& task) {
-	if (pdeIsSetUp) throw Exception("setUpPde called twice");
-	pdeIsSetUp = true;
-	HostState<D> st = buildHostState<D>(task, *this);
-	matrices = st.matrices;
-	maximalEigenvalue = st.maximalEigenvalue;
-	materialNumbers_ = st.materialNumber;
-	if (matrices.size() > 1) matIdAll_ = st.matId;
-	return st;
-}
-
-template <int D>
-typename HipMesh<D>::StackTable HipMesh<D>::stackTable(const std::vector<const HostState<D>*>& states) {
-	// one table over the members' material conditions; bitwise-equal ones shared
-	// (a stack of one material stays homogeneous: the non-HET one-pass step)
-	StackTable t;
-	t.remap.resize(states.size());
-	for (size_t k = 0; k < states.size(); k++)
-		for (size_t c = 0; c < states[k]->matrices.size(); c++) {
-			const GcmMatrices<D>& m = states[k]->matrices[c];
-			int found = -1;
-			for (size_t e = 0; e < t.table.size() && found < 0; e++)
-				if (std::memcmp(t.table[e], &m, sizeof(m)) == 0 && std::memcmp(&t.tau0[e], &states[k]->tau0[c], sizeof(real)) == 0)
-					found = (int)e;
-			if (found < 0) {
-				found = (int)t.table.size();
-				t.table.push_back(&m);
-				t.tau0.push_back(states[k]->tau0[c]);
-			}
-			t.remap[k].push_back(found);
-		}
-	if (t.table.size() > 255) throw Exception("a stack holds at most 255 materials");
-	return t;
-}
-
-template <int D>
-std::vector<int> HipMesh<D>::setStackMaterials(const StackTable& t, const std::vector<int>& used) {
-	const auto& table = t.table;
-	std::vector<int> dev(table.size(), -1);
-	int nUsed = 0;
-	for (size_t e = 0; e < table.size(); e++)
-		if (used[e]) dev[e] = nUsed++;
-	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
-	deviceTau0_.assign(nUsed, 0);
-	maximalEigenvalue = 0;
-	for (size_t e = 0; e < table.size(); e++) {
-		if (dev[e] < 0) continue;
-		deviceTau0_[dev[e]] = t.tau0[e];
-		maximalEigenvalue = std::fmax(maximalEigenvalue, table[e]->getMaximalEigenvalue());
-		for (int s = 0; s < D; s++) {
-			const size_t o = ((size_t)dev[e] * D + s);
-			std::copy(table[e]->m[s].U.begin(), table[e]->m[s].U.end(), U.begin() + o * M * M);
-			std::copy(table[e]->m[s].U1.begin(), table[e]->m[s].U1.end(), U1.begin() + o * M * M);
-			std::copy(table[e]->m[s].L.begin(), table[e]->m[s].L.end(), L.begin() + o * M);
-		}
-	}
-	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
-	return dev;
-}
-
-template <int D>
-void HipMesh<D>::setUpStack(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
-                            const std::vector<HostState<D>>& states) {
-	if (pdeIsSetUp) throw Exception("setUpPde called twice");
-	pdeIsSetUp = true;
-	std::vector<const HostState<D>*> sp;
-	for (const auto& st : states) sp.push_back(&st);
-	const StackTable tb = stackTable(sp);
-	const auto& remap = tb.remap;
-	// the stack's all-nodes state: every member's inner nodes and its ghost layers
-	// on the other axes; along the stack axis a member's ghost layers at a contact
-	// are its neighbour's inner layers (the stack's own ghosts only at its ends)
-	const int bs = this->borderSize, a = members.empty() ? 0 : members[0]->stackAxis_;
-	std::vector<real> pde((size_t)this->sizeOfAllNodes() * M, 0.0);
-	std::vector<uint8_t> ids((size_t)this->sizeOfAllNodes(), 0);
-	std::vector<int> used(tb.table.size(), 0);
-	for (size_t k = 0; k < members.size(); k++) {
-		const HipMesh<D>& mb = *members[k];
-		forEachAll<D>(mb.sizes, bs, [&](const IntD& it) {
-			if ((it[a] < 0 && k > 0) || (it[a] >= mb.sizes[a] && k + 1 < members.size())) return;
-			IntD is = it;
-			is[a] += mb.stackOffset_;
-			const size_t src = (size_t)mb.getIndex(it), dst = (size_t)this->getIndex(is);
-			for (int c = 0; c < M; c++) pde[dst * M + c] = states[k].pde[src * M + c];
-			const int t = remap[k][states[k].matId[src]];
-			ids[dst] = (uint8_t)t;
-			bool inner = true;
-			for (int d = 0; d < D; d++) inner = inner && it[d] >= 0 && it[d] < mb.sizes[d];
-			if (inner) used[(size_t)t] = 1;
-		});
-	}
-	const std::vector<int> dev = setStackMaterials(tb, used);
-	if (deviceTau0_.size() > 1) {
-		for (auto& m : ids) m = (uint8_t)std::max(0, dev[m]);
-		gcmxCheck(gcmx_set_material_ids(ctx_, ids.data()), "gcmx_set_material_ids");
-	}
-	gcmxCheck(gcmx_upload(ctx_, pde.data()), "gcmx_upload");
-}
-
 // ------------------------------------------------------- set-up on the device --
 
 gcmx_area deviceArea(const Area& area) {
@@ -362,132 +262,250 @@ std::vector<int> deviceCensus(gcmx_ctx* ctx, const gcmx_setup_box* box, const st
 
 }  // namespace
 
+// ----------------------------------------------------------------- placement --
+
 template <int D>
-gcmx_setup_box HipMesh<D>::setupBox(int axis, int offset) const {
+typename HipMesh<D>::PlacedBox HipMesh<D>::placeBox(const IntD& boxMin, const IntD& boxMax, int reach,
+                                                    const char* refusal) const {
+	for (int d = 0; d < D; d++)
+		if (boxMin[d] < -reach || boxMax[d] > this->sizes[d] + reach) throw Exception(refusal);
+	const IntD lo = inContext(boxMin), hi = inContext(boxMax);
+	PlacedBox p;
+	std::copy(lo.begin(), lo.end(), p.lo);
+	std::copy(hi.begin(), hi.end(), p.hi);
+	return p;
+}
+
+template <int D>
+gcmx_setup_box HipMesh<D>::setupBox() const {
+	const PlacedBox p = placeBox(IntD{}, this->sizes, 0, "setupBox");
 	gcmx_setup_box b{};
 	for (int d = 0; d < 3; d++) {
-		b.min[d] = 0;
-		b.max[d] = d < D ? this->sizes[d] : 1;
+		b.min[d] = p.lo[d];
+		b.max[d] = p.hi[d];
 		b.start[d] = d < D ? this->start[d] : 0;
-	}
-	if (axis >= 0) {
-		b.min[axis] += offset;
-		b.max[axis] += offset;
 	}
 	return b;
 }
 
-template <int D>
-void HipMesh<D>::setUpPdeOnDevice(const Task& task) {
-	SetUpLists<D> ls = buildSetUpLists<D>(task, *this);
-	const HostState<D>& st = ls.st;
-	if (st.model != model_) throw Exception("the body's model changed after its mesh was created");
-	matrices = st.matrices;
-	acousticMatrices = st.acousticMatrices;
-	maximalEigenvalue = st.maximalEigenvalue;
-	materialNumbers_ = st.materialNumber;
-	const size_t nCond = st.numberOfConditions();
-	const int M = st.M;
+// -------------------------------------------------------------------- set-up --
 
-	// ---- device tables: only the materials the nodes actually use (the census)
-	const std::vector<gcmx_area> areas = deviceAreas(ls.materialAreas);
-	std::vector<uint8_t> idOf(nCond);
-	for (size_t c = 0; c < nCond; c++) idOf[c] = (uint8_t)c;
-	const std::vector<int> used = deviceCensus(ctx_, nullptr, areas, idOf, nCond);
-	std::vector<int> remap(nCond, -1);
+template <int D, class Matrices>
+static typename MaterialTable<D>::Entry materialEntry(const Matrices& m, real tau0) {
+	typename MaterialTable<D>::Entry e{};
+	for (int s = 0; s < D; s++) {
+		e.U[s] = m.m[s].U.data();
+		e.U1[s] = m.m[s].U1.data();
+		e.L[s] = m.m[s].L.data();
+	}
+	e.bits = &m;
+	e.nBits = sizeof(m);
+	e.tau0 = tau0;
+	e.maximalEigenvalue = m.getMaximalEigenvalue();
+	return e;
+}
+
+template <int D>
+MaterialTable<D> buildMaterialTable(const std::vector<SetUpLists<D>>& lists, bool share) {
+	typedef typename MaterialTable<D>::Entry Entry;
+	MaterialTable<D> t;
+	t.entryOf.resize(lists.size());
+	for (size_t k = 0; k < lists.size(); k++) {
+		const HostState<D>& st = lists[k].st;
+		t.M = st.M;
+		for (size_t c = 0; c < st.numberOfConditions(); c++) {
+			const Entry e = st.model == Models::T::ACOUSTIC ? materialEntry<D>(st.acousticMatrices[c], st.tau0[c])
+			                                                : materialEntry<D>(st.matrices[c], st.tau0[c]);
+			int found = -1;
+			for (size_t i = 0; share && i < t.entries.size() && found < 0; i++) {
+				const Entry& o = t.entries[i];
+				if (o.nBits == e.nBits && std::memcmp(o.bits, e.bits, e.nBits) == 0 &&
+				    std::memcmp(&o.tau0, &e.tau0, sizeof(real)) == 0)
+					found = (int)i;
+			}
+			if (found < 0) {
+				found = (int)t.entries.size();
+				t.entries.push_back(e);
+			}
+			t.entryOf[k].push_back(found);
+		}
+	}
+	// (a lone body cannot get here: buildSetUpLists holds it to 255 conditions)
+	if (t.entries.size() > 255) throw Exception("a stack holds at most 255 materials");
+	return t;
+}
+
+template <int D>
+std::vector<int> HipMesh<D>::sendMaterials(const MaterialTable<D>& table, const std::vector<int>& used) {
+	const size_t n = table.entries.size(), M = (size_t)table.M;
+	std::vector<int> dev(n, -1);
 	int nUsed = 0;
-	for (size_t c = 0; c < nCond; c++)
-		if (used[c]) remap[c] = nUsed++;
+	for (size_t e = 0; e < n; e++)
+		if (used[e]) dev[e] = nUsed++;
 	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
 	deviceTau0_.assign(nUsed, 0);
-	for (size_t c = 0; c < nCond; c++) {
-		if (remap[c] < 0) continue;
-		deviceTau0_[remap[c]] = st.tau0[c];
+	for (size_t e = 0; e < n; e++) {
+		if (dev[e] < 0) continue;
+		deviceTau0_[dev[e]] = table.entries[e].tau0;
 		for (int s = 0; s < D; s++) {
-			const size_t o = ((size_t)remap[c] * D + s);
-			if (model_ == Models::T::ACOUSTIC) {
-				const auto& m = acousticMatrices[c].m[s];
-				std::copy(m.U.begin(), m.U.end(), U.begin() + o * M * M);
-				std::copy(m.U1.begin(), m.U1.end(), U1.begin() + o * M * M);
-				std::copy(m.L.begin(), m.L.end(), L.begin() + o * M);
-				continue;
-			}
-			std::copy(matrices[c].m[s].U.begin(), matrices[c].m[s].U.end(), U.begin() + o * M * M);
-			std::copy(matrices[c].m[s].U1.begin(), matrices[c].m[s].U1.end(), U1.begin() + o * M * M);
-			std::copy(matrices[c].m[s].L.begin(), matrices[c].m[s].L.end(), L.begin() + o * M);
+			const size_t o = (size_t)dev[e] * D + s;
+			std::copy_n(table.entries[e].U[s], M * M, U.begin() + o * M * M);
+			std::copy_n(table.entries[e].U1[s], M * M, U1.begin() + o * M * M);
+			std::copy_n(table.entries[e].L[s], M, L.begin() + o * M);
 		}
 	}
 	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
-	if (nUsed > 1) {
-		for (size_t c = 0; c < nCond; c++) idOf[c] = (uint8_t)std::max(0, remap[c]);
-		gcmxCheck(gcmx_setup_material_ids(ctx_, nullptr, (int)areas.size(), areas.data(), idOf.data()),
-		          "gcmx_setup_material_ids");
-	}
-	deviceInitialState<D>(ctx_, nullptr, ls);
-	if (nCond > 1) {  // the snapshotters' material array: from the device on first use
-		idsOnDevice_ = true;
-		materialAreas_ = ls.materialAreas;
-		conditionOfDeviceId_.assign(256, -1);
-		for (size_t c = 0; c < nCond; c++)
-			if (remap[c] >= 0) conditionOfDeviceId_[(size_t)remap[c]] = (int)c;
-	}
+	return dev;
 }
 
+/// What differs between the set-up on the host and on the device: the node loops.
 template <int D>
-SetUpLists<D> HipMesh<D>::setUpMemberOnDevice(const Task& task) {
-	if (pdeIsSetUp) throw Exception("setUpPde called twice");
-	pdeIsSetUp = true;
-	SetUpLists<D> ls = buildSetUpLists<D>(task, *this);
-	matrices = ls.st.matrices;
-	maximalEigenvalue = ls.st.maximalEigenvalue;
-	materialNumbers_ = ls.st.materialNumber;
-	return ls;
-}
+struct HipMesh<D>::NodePass {
+	HipMesh<D>& owner;  // the mesh of the context
+	const std::vector<HipMesh<D>*>& members;
+	const std::vector<SetUpLists<D>>& lists;
+	const MaterialTable<D>& table;
+	NodePass(HipMesh<D>& o, const std::vector<HipMesh<D>*>& m, const std::vector<SetUpLists<D>>& l,
+	         const MaterialTable<D>& t)
+	    : owner(o), members(m), lists(l), table(t) {}
+	virtual ~NodePass() = default;
+	/// Per table entry: whether an inner node has it.
+	virtual std::vector<int> census() = 0;
+	/// Ids (where more than one material went to the device) and state, given
+	/// entry -> device id; an unused entry's nodes -- ghosts only -- take id 0.
+	virtual void place(const std::vector<int>& dev) = 0;
+};
 
+/// The node arrays of the context on the host, one gcmx_set_material_ids and one
+/// gcmx_upload: every member's inner nodes and its ghost layers on the other axes;
+/// along the stack axis a member's ghost layers at a contact are its neighbour's
+/// inner layers (the stack's own ghosts only at its ends).
 template <int D>
-void HipMesh<D>::setUpStackOnDevice(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
-                                    const std::vector<SetUpLists<D>>& lists) {
-	if (pdeIsSetUp) throw Exception("setUpPde called twice");
-	pdeIsSetUp = true;
-	std::vector<const HostState<D>*> sp;
-	for (const auto& ls : lists) sp.push_back(&ls.st);
-	const StackTable tb = stackTable(sp);
-	// every member's census over its own box of the stack, with its own start: the
-	// stack's ghosts and the contact layers need nothing beyond the members' inner nodes
-	std::vector<int> used(tb.table.size(), 0);
-	std::vector<std::vector<gcmx_area>> areas(members.size());
-	std::vector<gcmx_setup_box> boxes(members.size());
-	for (size_t k = 0; k < members.size(); k++) {
-		const HipMesh<D>& mb = *members[k];
-		areas[k] = deviceAreas(lists[k].materialAreas);
-		boxes[k] = mb.setupBox(mb.stackAxis_, mb.stackOffset_);
-		std::vector<uint8_t> idOf;
-		for (int t : tb.remap[k]) idOf.push_back((uint8_t)t);
-		const std::vector<int> mine = deviceCensus(ctx_, &boxes[k], areas[k], idOf, tb.table.size());
-		for (size_t t = 0; t < used.size(); t++) used[t] = used[t] || mine[t];
-	}
-	const std::vector<int> dev = setStackMaterials(tb, used);
-	for (size_t k = 0; k < members.size(); k++) {
-		HipMesh<D>& mb = *members[k];
-		if (deviceTau0_.size() > 1) {
-			std::vector<uint8_t> idOf;
-			for (int t : tb.remap[k]) idOf.push_back((uint8_t)std::max(0, dev[(size_t)t]));
-			gcmxCheck(gcmx_setup_material_ids(ctx_, &boxes[k], (int)areas[k].size(), areas[k].data(), idOf.data()),
-			          "gcmx_setup_material_ids");
+struct HipMesh<D>::HostNodePass : NodePass {
+	using NodePass::NodePass;
+	std::vector<real> pde;
+	std::vector<uint8_t> ids;  // table entries, then device ids
+	std::vector<int> census() override {
+		const HipMesh<D>& owner = this->owner;
+		std::vector<int> used(this->table.entries.size(), 0);
+		pde.assign((size_t)owner.sizeOfAllNodes() * this->table.M, 0.0);
+		ids.assign((size_t)owner.sizeOfAllNodes(), 0);
+		for (size_t k = 0; k < this->members.size(); k++) {
+			HipMesh<D>& mb = *this->members[k];
+			const bool first = k == 0, last = k + 1 == this->members.size();
+			const std::vector<int>& entryOf = this->table.entryOf[k];
+			std::vector<uint8_t> cond((size_t)mb.sizeOfAllNodes(), 0);
+			applySetUpLists<D>(this->lists[k], mb, cond, owner, mb.inContext(IntD{}), pde);
+			const int a = mb.stackAxis_;
+			forEachAll<D>(mb.sizes, mb.borderSize, [&](const IntD& it) {
+				if (a >= 0 && ((it[a] < 0 && !first) || (it[a] >= mb.sizes[a] && !last))) return;
+				const int e = entryOf[cond[(size_t)mb.getIndex(it)]];
+				ids[(size_t)owner.getIndex(mb.inContext(it))] = (uint8_t)e;
+				bool inner = true;
+				for (int d = 0; d < D; d++) inner = inner && it[d] >= 0 && it[d] < mb.sizes[d];
+				if (inner) used[(size_t)e] = 1;
+			});
+			// the snapshots' material array: condition indices, not device ids
+			if (entryOf.size() > 1) mb.matIdAll_ = std::move(cond);
 		}
-		deviceInitialState<D>(ctx_, &boxes[k], lists[k]);
-		if (mb.matrices.size() > 1) {
-			mb.idsOnDevice_ = true;
-			mb.materialAreas_ = lists[k].materialAreas;
+		return used;
+	}
+	void place(const std::vector<int>& dev) override {
+		if (this->owner.deviceTau0_.size() > 1) {
+			for (auto& e : ids) e = (uint8_t)std::max(0, dev[e]);
+			gcmxCheck(gcmx_set_material_ids(this->owner.ctx_, ids.data()), "gcmx_set_material_ids");
+		}
+		gcmxCheck(gcmx_upload(this->owner.ctx_, pde.data()), "gcmx_upload");
+	}
+};
+
+/// Census, ids and state on the device, once per member over the member's box of
+/// the context with its own start: the context's ghosts and the contact layers
+/// need nothing beyond the members' inner nodes.  No gcmx_upload, and no host
+/// array the size of the grid; a member's ids wait on the device until a snapshot
+/// asks for them (fetchMaterialIds).
+template <int D>
+struct HipMesh<D>::DeviceNodePass : NodePass {
+	using NodePass::NodePass;
+	std::vector<std::vector<gcmx_area>> areas;
+	std::vector<gcmx_setup_box> boxes;
+	std::vector<int> census() override {
+		std::vector<int> used(this->table.entries.size(), 0);
+		for (size_t k = 0; k < this->members.size(); k++) {
+			areas.push_back(deviceAreas(this->lists[k].materialAreas));
+			boxes.push_back(this->members[k]->setupBox());
+			const std::vector<int>& entryOf = this->table.entryOf[k];
+			const std::vector<int> mine = deviceCensus(this->owner.ctx_, &boxes[k], areas[k],
+			                                           std::vector<uint8_t>(entryOf.begin(), entryOf.end()), used.size());
+			for (size_t e = 0; e < used.size(); e++) used[e] = used[e] || mine[e];
+		}
+		return used;
+	}
+	void place(const std::vector<int>& dev) override {
+		gcmx_ctx* ctx = this->owner.ctx_;
+		for (size_t k = 0; k < this->members.size(); k++) {
+			HipMesh<D>& mb = *this->members[k];
+			const std::vector<int>& entryOf = this->table.entryOf[k];
+			if (this->owner.deviceTau0_.size() > 1) {
+				std::vector<uint8_t> idOf;
+				for (int e : entryOf) idOf.push_back((uint8_t)std::max(0, dev[(size_t)e]));
+				gcmxCheck(gcmx_setup_material_ids(ctx, &boxes[k], (int)areas[k].size(), areas[k].data(), idOf.data()),
+				          "gcmx_setup_material_ids");
+			}
+			deviceInitialState<D>(ctx, &boxes[k], this->lists[k]);
+			if (entryOf.size() < 2) continue;
+			mb.idsOnDevice_ = true;  // the snapshotters' material array: from the device on first use
+			mb.materialAreas_ = this->lists[k].materialAreas;
 			mb.conditionOfDeviceId_.assign(256, -1);
-			for (size_t c = 0; c < tb.remap[k].size(); c++) {
-				const int d = dev[(size_t)tb.remap[k][c]];
+			for (size_t c = 0; c < entryOf.size(); c++) {
+				const int d = dev[(size_t)entryOf[c]];
 				if (d < 0) continue;
 				int& slot = mb.conditionOfDeviceId_[(size_t)d];
 				slot = slot == -1 ? (int)c : -2;  // two conditions of one material: the device cannot tell them apart
 			}
 		}
 	}
+};
+
+template <int D>
+void HipMesh<D>::markSetUp() {
+	if (pdeIsSetUp) throw Exception("setUpPde called twice");
+	pdeIsSetUp = true;
+}
+
+template <int D>
+SetUpLists<D> HipMesh<D>::setUpMember(const Task& task) {
+	markSetUp();
+	SetUpLists<D> ls = buildSetUpLists<D>(task, *this);
+	if (ls.st.model != model_) throw Exception("the body's model changed after its mesh was created");
+	maximalEigenvalue = ls.st.maximalEigenvalue;  // over all its conditions, used or not: the time step reads it
+	materialNumbers_ = ls.st.materialNumber;
+	return ls;
+}
+
+template <int D>
+void HipMesh<D>::setUp(const std::vector<HipMesh<D>*>& members, const std::vector<SetUpLists<D>>& lists, bool onDevice) {
+	const bool stack = members.front() != this;  // or this mesh itself, as a stack of one
+	if (stack) markSetUp();
+	// a stack of one material stays homogeneous (the non-HET one-pass step); a lone
+	// body keeps one device material per condition that holds nodes
+	const MaterialTable<D> table = buildMaterialTable<D>(lists, stack);
+	std::unique_ptr<NodePass> pass;
+	if (onDevice) pass.reset(new DeviceNodePass(*this, members, lists, table));
+	else pass.reset(new HostNodePass(*this, members, lists, table));
+	const std::vector<int> dev = sendMaterials(table, pass->census());
+	if (stack)  // the stack mesh's own eigenvalue: over the entries in use
+		for (size_t e = 0; e < dev.size(); e++)
+			if (dev[e] >= 0) maximalEigenvalue = std::fmax(maximalEigenvalue, table.entries[e].maximalEigenvalue);
+	pass->place(dev);
+}
+
+// DefaultMesh::setUpPde (DefaultMesh.hpp:60-66): a lone body is a stack of one.
+template <int D>
+void HipMesh<D>::setUpPde(const Task& task) {
+	std::vector<SetUpLists<D>> lists;
+	lists.push_back(setUpMember(task));
+	setUp({this}, lists, task.cubicGrid.setUpOnDevice);
 }
 
 template <int D>
@@ -498,9 +516,7 @@ void HipMesh<D>::fetchMaterialIds() const {
 	gcmxCheck(gcmx_download_material_ids(ctx_, all.data()), "gcmx_download_material_ids");
 	matIdAll_.assign((size_t)this->sizeOfAllNodes(), 0);
 	forEachInner<D>(this->sizes, [&](const IntD& it) {
-		IntD is = it;
-		if (stack_) is[stackAxis_] += stackOffset_;
-		int c = conditionOfDeviceId_[all[(size_t)owner.getIndex(is)]];
+		int c = conditionOfDeviceId_[all[(size_t)owner.getIndex(inContext(it))]];
 		if (c == -2) {  // MaterialsCondition::apply for this node on the host
 			const Real3 x = this->coords(it);
 			for (size_t k = 0; k < materialAreas_.size(); k++)
@@ -532,13 +548,18 @@ typename CubicGrid<D>::ConstructionPack constructionPack(const Task& task, size_
 template <int D>
 HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 	SetUpLists<D> ls = buildSetUpLists<D>(task, grid);
-	HostState<D> st = std::move(ls.st);
-	const int M = st.M;
-	const long long nAll = grid.sizeOfAllNodes();
-	st.pde.assign((size_t)nAll * M, 0.0);
-	st.matId.assign((size_t)nAll, 0);
-	auto& pde = st.pde;
-	auto& matId = st.matId;
+	std::vector<real> pde((size_t)grid.sizeOfAllNodes() * ls.st.M, 0.0);
+	std::vector<uint8_t> matId((size_t)grid.sizeOfAllNodes(), 0);
+	applySetUpLists<D>(ls, grid, matId, grid, std::array<int, D>{}, pde);
+	ls.st.pde = std::move(pde);
+	ls.st.matId = std::move(matId);
+	return std::move(ls.st);
+}
+
+template <int D>
+void applySetUpLists(const SetUpLists<D>& ls, const CubicGrid<D>& grid, std::vector<uint8_t>& matId,
+                     const CubicGrid<D>& layer, const std::array<int, D>& shift, std::vector<real>& pde) {
+	const int M = ls.st.M;
 	// ---- MaterialsCondition::apply, the node loop (MaterialsCondition.hpp:23-36)
 	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
 		const Real3 x = grid.coords(it);
@@ -548,13 +569,14 @@ HostState<D> buildHostState(const Task& task, const CubicGrid<D>& grid) {
 	// ---- InitialCondition::apply, the node loop (InitialCondition.hpp:23-88)
 	forEachInner<D>(grid.sizes, [&](const std::array<int, D>& it) {
 		const Real3 x = grid.coords(it);
-		real* v = &pde[(size_t)grid.getIndex(it) * M];
+		std::array<int, D> at = it;
+		for (int d = 0; d < D; d++) at[d] += shift[d];
+		real* v = &pde[(size_t)layer.getIndex(at) * M];
 		for (int c = 0; c < M; c++) v[c] = 0;
 		for (const auto& ic : ls.initial)
 			if (ic.first->contains(x))
 				for (int c = 0; c < M; c++) v[c] += ic.second[c];
 	});
-	return st;
 }
 
 template <int D>
@@ -662,56 +684,6 @@ SetUpLists<D> buildSetUpLists(const Task& task, const CubicGrid<D>& grid) {
 }
 
 template <int D>
-void HipMesh<D>::setUpPde(const Task& task) {
-	if (pdeIsSetUp) throw Exception("setUpPde called twice");
-	pdeIsSetUp = true;
-	if (task.cubicGrid.setUpOnDevice) return setUpPdeOnDevice(task);
-	HostState<D> st = buildHostState<D>(task, *this);
-	if (st.model != model_) throw Exception("the body's model changed after its mesh was created");
-	matrices = st.matrices;
-	acousticMatrices = st.acousticMatrices;
-	maximalEigenvalue = st.maximalEigenvalue;
-	auto& matId = st.matId;
-	materialNumbers_ = st.materialNumber;
-	const size_t nCond = st.numberOfConditions();
-	const int M = st.M;  // the model's components per node
-	if (nCond > 1) matIdAll_ = matId;  // before the device remap below
-
-	// ---- device tables: only the materials the nodes actually use
-	std::vector<int> used(nCond, 0);
-	forEachInner<D>(this->sizes, [&](const IntD& it) { used[matId[(size_t)this->getIndex(it)]] = 1; });
-	std::vector<int> remap(nCond, -1);
-	int nUsed = 0;
-	for (size_t c = 0; c < nCond; c++)
-		if (used[c]) remap[c] = nUsed++;
-	std::vector<real> U((size_t)nUsed * D * M * M), U1(U.size()), L((size_t)nUsed * D * M);
-	deviceTau0_.assign(nUsed, 0);
-	for (size_t c = 0; c < nCond; c++) {
-		if (remap[c] < 0) continue;
-		deviceTau0_[remap[c]] = st.tau0[c];
-		for (int s = 0; s < D; s++) {
-			const size_t o = ((size_t)remap[c] * D + s);
-			if (model_ == Models::T::ACOUSTIC) {
-				const auto& m = acousticMatrices[c].m[s];
-				std::copy(m.U.begin(), m.U.end(), U.begin() + o * M * M);
-				std::copy(m.U1.begin(), m.U1.end(), U1.begin() + o * M * M);
-				std::copy(m.L.begin(), m.L.end(), L.begin() + o * M);
-				continue;
-			}
-			std::copy(matrices[c].m[s].U.begin(), matrices[c].m[s].U.end(), U.begin() + o * M * M);
-			std::copy(matrices[c].m[s].U1.begin(), matrices[c].m[s].U1.end(), U1.begin() + o * M * M);
-			std::copy(matrices[c].m[s].L.begin(), matrices[c].m[s].L.end(), L.begin() + o * M);
-		}
-	}
-	gcmxCheck(gcmx_set_materials(ctx_, nUsed, U.data(), U1.data(), L.data()), "gcmx_set_materials");
-	if (nUsed > 1) {
-		for (auto& m : matId) m = (uint8_t)std::max(0, remap[m]);
-		gcmxCheck(gcmx_set_material_ids(ctx_, matId.data()), "gcmx_set_material_ids");
-	}
-	gcmxCheck(gcmx_upload(ctx_, st.pde.data()), "gcmx_upload");
-}
-
-template <int D>
 std::vector<real> HipMesh<D>::pdeAll() const {
 	// the all-nodes box; for a stack member its part of the stack (its ghost layers
 	// at a contact: the neighbour's inner layers, as the contact copy leaves them)
@@ -727,27 +699,14 @@ std::vector<real> HipMesh<D>::pdeAll() const {
 
 template <int D>
 void HipMesh<D>::readBox(const IntD& boxMin, const IntD& boxMax, real* aos, size_t stageBytes) const {
-	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
-	for (int d = 0; d < D; d++) {
-		if (boxMin[d] < -this->borderSize || boxMax[d] > this->sizes[d] + this->borderSize)
-			throw Exception("readBox: box outside the nodes of the mesh");
-		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
-		lo[d] = boxMin[d] + off;
-		hi[d] = boxMax[d] + off;
-	}
-	gcmxCheck(gcmx_read_box(ctx_, lo, hi, aos, stageBytes), "gcmx_read_box");
+	const PlacedBox p = placeBox(boxMin, boxMax, this->borderSize, "readBox: box outside the nodes of the mesh");
+	gcmxCheck(gcmx_read_box(ctx_, p.lo, p.hi, aos, stageBytes), "gcmx_read_box");
 }
 
 template <int D>
 void HipMesh<D>::writeBox(const IntD& boxMin, const IntD& boxMax, const real* aos, size_t stageBytes) {
-	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
-	for (int d = 0; d < D; d++) {
-		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("writeBox: only inner nodes can be written");
-		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
-		lo[d] = boxMin[d] + off;
-		hi[d] = boxMax[d] + off;
-	}
-	gcmxCheck(gcmx_write_box(ctx_, lo, hi, aos, stageBytes), "gcmx_write_box");
+	const PlacedBox p = placeBox(boxMin, boxMax, 0, "writeBox: only inner nodes can be written");
+	gcmxCheck(gcmx_write_box(ctx_, p.lo, p.hi, aos, stageBytes), "gcmx_write_box");
 }
 
 template <int D>
@@ -767,11 +726,12 @@ template <int D>
 std::shared_ptr<typename HipMesh<D>::NodeList> HipMesh<D>::nodeList(const std::vector<IntD>& nodes) const {
 	std::vector<int> flat;
 	flat.reserve(nodes.size() * D);
-	for (const IntD& it : nodes)
-		for (int d = 0; d < D; d++) {
-			if (it[d] < 0 || it[d] >= this->sizes[d]) throw Exception("nodeList: only inner nodes can be observed");
-			flat.push_back(it[d] + (stack_ && d == stackAxis_ ? stackOffset_ : 0));
-		}
+	for (const IntD& it : nodes) {
+		IntD next = it;
+		for (int d = 0; d < D; d++) next[d]++;
+		const PlacedBox p = placeBox(it, next, 0, "nodeList: only inner nodes can be observed");
+		flat.insert(flat.end(), p.lo, p.lo + D);
+	}
 	auto list = std::make_shared<NodeList>();
 	gcmxCheck(gcmx_node_list_create(ctx_, (int)nodes.size(), flat.data(), &list->handle), "gcmx_node_list_create");
 	list->size = nodes.size();
@@ -779,23 +739,10 @@ std::shared_ptr<typename HipMesh<D>::NodeList> HipMesh<D>::nodeList(const std::v
 }
 
 template <int D>
-std::vector<real> HipMesh<D>::gather(const NodeList& nodes, const std::vector<int>& quantities) const {
-	std::vector<real> out(quantities.size() * nodes.size);
-	gcmxCheck(gcmx_gather(ctx_, nodes.handle, (int)quantities.size(), quantities.data(), out.data()), "gcmx_gather");
-	return out;
-}
-
-template <int D>
 void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const std::vector<int>& quantities,
                                 float* velocity, float* values) const {
-	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
-	for (int d = 0; d < D; d++) {
-		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("snapshotArrays: only inner nodes can be observed");
-		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
-		lo[d] = boxMin[d] + off;
-		hi[d] = boxMax[d] + off;
-	}
-	gcmxCheck(gcmx_snapshot_box(ctx_, lo, hi, velocity ? 1 : 0, (int)quantities.size(), quantities.data(), velocity,
+	const PlacedBox p = placeBox(boxMin, boxMax, 0, "snapshotArrays: only inner nodes can be observed");
+	gcmxCheck(gcmx_snapshot_box(ctx_, p.lo, p.hi, velocity ? 1 : 0, (int)quantities.size(), quantities.data(), velocity,
 	                            values),
 	          "gcmx_snapshot_box");
 }
@@ -803,17 +750,19 @@ void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const st
 template <int D>
 void HipMesh<D>::snapshotArrays(const IntD& boxMin, const IntD& boxMax, const IntD& stride,
                                 const std::vector<int>& quantities, float* velocity, float* values) const {
-	int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1}, st[3] = {1, 1, 1};
-	for (int d = 0; d < D; d++) {
-		if (boxMin[d] < 0 || boxMax[d] > this->sizes[d]) throw Exception("snapshotArrays: only inner nodes can be observed");
-		const int off = stack_ && d == stackAxis_ ? stackOffset_ : 0;
-		lo[d] = boxMin[d] + off;
-		hi[d] = boxMax[d] + off;
-		st[d] = stride[d];
-	}
-	gcmxCheck(gcmx_snapshot_strided(ctx_, lo, hi, st, velocity ? 1 : 0, (int)quantities.size(), quantities.data(),
+	const PlacedBox p = placeBox(boxMin, boxMax, 0, "snapshotArrays: only inner nodes can be observed");
+	int st[3] = {1, 1, 1};
+	std::copy(stride.begin(), stride.end(), st);
+	gcmxCheck(gcmx_snapshot_strided(ctx_, p.lo, p.hi, st, velocity ? 1 : 0, (int)quantities.size(), quantities.data(),
 	                                velocity, values),
 	          "gcmx_snapshot_strided");
+}
+
+template <int D>
+std::vector<real> HipMesh<D>::gather(const NodeList& nodes, const std::vector<int>& quantities) const {
+	std::vector<real> out(quantities.size() * nodes.size);
+	gcmxCheck(gcmx_gather(ctx_, nodes.handle, (int)quantities.size(), quantities.data(), out.data()), "gcmx_gather");
+	return out;
 }
 
 template <int D>
@@ -998,35 +947,26 @@ Engine<D>::Engine(const Task& task, int device_)
 	if (task.globalSettings.dimensionality != D) throw Exception("dimensionality mismatch");
 	createGridsAndContacts(task);
 	buildStacks(task);
-	const bool onDevice = task.cubicGrid.setUpOnDevice;
-	std::map<size_t, HostState<D>> memberStates;
-	std::map<size_t, SetUpLists<D>> memberLists;
+	std::map<size_t, SetUpLists<D>> memberLists;  // of the bodies in stacks
 	for (const auto& tb : task.bodies) {
 		Body& body = getBody(tb.first);
-		if (body.stack && onDevice)
-			memberLists.emplace(tb.first, std::dynamic_pointer_cast<HipMesh<D>>(body.mesh)->setUpMemberOnDevice(task));
-		else if (body.stack)
-			memberStates.emplace(tb.first, std::dynamic_pointer_cast<HipMesh<D>>(body.mesh)->setUpMember(task));
-		else
-			body.mesh->setUpPde(task);
+		if (body.stack) memberLists.emplace(tb.first, dynamic_cast<HipMesh<D>&>(*body.mesh).setUpMember(task));
+		else body.mesh->setUpPde(task);
 		body.gcm = body.factory->createGcm(task);
 		body.border = body.factory->createBorder(task, body.mesh);
 		for (const Snapshotters::T snapType : task.globalSettings.snapshottersId)
 			body.snapshotters.push_back(body.factory->createSnapshotter(task, snapType));
 		for (const Odes::T odeType : tb.second.odes) body.odes.push_back(body.factory->createOde(odeType));
 	}
-	for (Body& lead : bodies) {  // every stack's set-up from its members' host states
+	for (Body& lead : bodies) {  // every stack's set-up from its members' lists
 		if (!lead.stackLead) continue;
-		std::vector<std::shared_ptr<HipMesh<D>>> members;
-		std::vector<HostState<D>> states;
+		std::vector<HipMesh<D>*> members;
 		std::vector<SetUpLists<D>> lists;
 		for (size_t id : stackOrder_.at(lead.mesh->id)) {
-			members.push_back(std::dynamic_pointer_cast<HipMesh<D>>(getBody(id).mesh));
-			if (onDevice) lists.push_back(std::move(memberLists.at(id)));
-			else states.push_back(std::move(memberStates.at(id)));
+			members.push_back(&dynamic_cast<HipMesh<D>&>(*getBody(id).mesh));
+			lists.push_back(std::move(memberLists.at(id)));
 		}
-		if (onDevice) lead.stack->setUpStackOnDevice(members, lists);
-		else lead.stack->setUpStack(members, states);
+		lead.stack->setUp(members, lists, task.cubicGrid.setUpOnDevice);
 	}
 	afterConstruction(task);
 }
@@ -1566,6 +1506,15 @@ template HostState<3> buildHostState<3>(const Task&, const CubicGrid<3>&);
 template SetUpLists<1> buildSetUpLists<1>(const Task&, const CubicGrid<1>&);
 template SetUpLists<2> buildSetUpLists<2>(const Task&, const CubicGrid<2>&);
 template SetUpLists<3> buildSetUpLists<3>(const Task&, const CubicGrid<3>&);
+template void applySetUpLists<1>(const SetUpLists<1>&, const CubicGrid<1>&, std::vector<uint8_t>&, const CubicGrid<1>&,
+                                  const std::array<int, 1>&, std::vector<real>&);
+template void applySetUpLists<2>(const SetUpLists<2>&, const CubicGrid<2>&, std::vector<uint8_t>&, const CubicGrid<2>&,
+                                  const std::array<int, 2>&, std::vector<real>&);
+template void applySetUpLists<3>(const SetUpLists<3>&, const CubicGrid<3>&, std::vector<uint8_t>&, const CubicGrid<3>&,
+                                  const std::array<int, 3>&, std::vector<real>&);
+template MaterialTable<1> buildMaterialTable<1>(const std::vector<SetUpLists<1>>&, bool);
+template MaterialTable<2> buildMaterialTable<2>(const std::vector<SetUpLists<2>>&, bool);
+template MaterialTable<3> buildMaterialTable<3>(const std::vector<SetUpLists<3>>&, bool);
 template class Engine<1>;
 template class Engine<2>;
 template class Engine<3>;

@@ -174,11 +174,51 @@ struct SetUpLists {
 template <int D>
 SetUpLists<D> buildSetUpLists(const Task& task, const CubicGrid<D>& grid);
 
+/// The per-node half: the two node loops of MaterialsCondition::apply and
+/// InitialCondition::apply over the inner nodes of `grid`.  matId (zeros, the
+/// grid's all-nodes size) takes the condition of every node; pde (zeros) takes
+/// the state at layer.getIndex(it + shift), the node's place in the layer that
+/// receives it: the grid itself, or the stack the grid is a member of.
+/// buildHostState is buildSetUpLists followed by this.
+template <int D>
+void applySetUpLists(const SetUpLists<D>& ls, const CubicGrid<D>& grid, std::vector<uint8_t>& matId,
+                     const CubicGrid<D>& layer, const std::array<int, D>& shift, std::vector<real>& pde);
+
+/// One table over the material conditions of the bodies that share a context.
+/// An entry views the matrices of a condition of either model (they stay in the
+/// SetUpLists the table was built from).
+template <int D>
+struct MaterialTable {
+	struct Entry {
+		const real *U[D], *U1[D], *L[D];  // per axis: M * M, M * M and M values
+		const void* bits;                 // the condition's whole matrices, to compare
+		size_t nBits;
+		real tau0, maximalEigenvalue;
+	};
+	int M = pdeSize(D);
+	std::vector<Entry> entries;
+	std::vector<std::vector<int>> entryOf;  // [member][condition] -> entry
+};
+/// `share`: bitwise-equal conditions (matrices and tau0) take one entry.
+template <int D>
+MaterialTable<D> buildMaterialTable(const std::vector<SetUpLists<D>>& lists, bool share);
+
 /// An Area as the device knows it (gcmx_area); throws for a kind it does not.
 gcmx_area deviceArea(const Area& area);
 
 /// DefaultMesh's role with GPU-resident storage: the context owns both time
 /// layers on the device; the host holds only set-up data.
+///
+/// SET-UP has one path, setUp(members, lists, onDevice), for the bodies that
+/// share this mesh's context: the members of a stack, or the mesh itself as a
+/// stack of one at offset 0 (setUpPde).  Every member first builds its matrices
+/// and condition lists (setUpMember).  The path then makes one MaterialTable,
+/// lets a node pass find the entries that hold inner nodes, sends those to the
+/// device (sendMaterials), and lets the pass set the ids (only if more than one
+/// material is in use) and the state.  The two passes differ in where the node
+/// loops run: HostNodePass fills all-nodes arrays on the host and uploads one
+/// layer; DeviceNodePass hands the members' areas to the device box by box and
+/// allocates nothing the size of the grid.  DESIGN.md 3.6.1 lists the rules kept.
 template <int D>
 class HipMesh : public AbstractMesh<D> {
 public:
@@ -190,8 +230,7 @@ public:
 	HipMesh(const Task& task, size_t id, const typename CubicGrid<D>::ConstructionPack& cp,
 	        int device);
 	~HipMesh() override;
-	/// DefaultMesh::setUpPde (DefaultMesh.hpp:60-66): allocate, MaterialsCondition,
-	/// InitialCondition, then upload.
+	/// DefaultMesh::setUpPde (DefaultMesh.hpp:60-66): setUpMember, then setUp({this}).
 	void setUpPde(const Task& task) override;
 	real getMaximalEigenvalue() const override { return maximalEigenvalue; }
 	/// The device swap happens inside gcmx_stage; nothing to do here.
@@ -236,7 +275,7 @@ public:
 	                    float* velocity, float* values) const;
 	/// Bytes the body's context copied {device -> host, host -> device} (gcmx_transfer_stats).
 	std::array<uint64_t, 2> transferBytes() const;
-	int numberOfMaterials() const { return (int)(model_ == Models::T::ACOUSTIC ? acousticMatrices.size() : matrices.size()); }
+	int numberOfMaterials() const { return (int)materialNumbers_.size(); }
 	/// tau0 of the materials in the device table order (gcmx_set_materials).
 	const std::vector<real>& deviceTau0() const { return deviceTau0_; }
 	/// Material-condition index per node (all-nodes order) and the conditions'
@@ -257,20 +296,18 @@ public:
 	/// the stack's stage reads there anyway -- so every inner node is bitwise that
 	/// of the separate bodies (TestEngine.cpp:27-87 pins split == unsplit), and the
 	/// step keeps the one-pass kernel instead of three per-stage passes.  A member
-	/// keeps its own host data (set-up, materials, snapshots) and reads its part of
-	/// the stack's device layers; the stack is a HipMesh over the combined box.
+	/// keeps its own host data (materials, snapshots) and reads its part of the
+	/// stack's device layers; the stack is a HipMesh over the combined box, set up
+	/// from its members' lists (setUp).  A member's ghost layers at a contact are
+	/// its neighbour's inner layers.
 	void joinStack(const std::shared_ptr<HipMesh<D>>& stack, int axis, int offset);
 	const std::shared_ptr<HipMesh<D>>& stackMesh() const { return stack_; }
-	/// A stack member's DefaultMesh::setUpPde, host half only (the stack uploads).
-	HostState<D> setUpMember(const Task& task);
-	/// The stack's set-up from its members' host states, members in stack order.
-	void setUpStack(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
-	                const std::vector<HostState<D>>& states);
-	/// The same two with the node loops on the device: a member keeps its lists,
-	/// the stack runs census, ids and state once per member over the member's box.
-	SetUpLists<D> setUpMemberOnDevice(const Task& task);
-	void setUpStackOnDevice(const std::vector<std::shared_ptr<HipMesh<D>>>& members,
-	                        const std::vector<SetUpLists<D>>& lists);
+	/// The per-condition half of a body's set-up (its own or a stack member's):
+	/// the lists, its eigenvalue over ALL its conditions, its material numbers.
+	SetUpLists<D> setUpMember(const Task& task);
+	/// The set-up of this mesh's context from the bodies in it, in stack order,
+	/// with the node loops on the host or on the device (see the class comment).
+	void setUp(const std::vector<HipMesh<D>*>& members, const std::vector<SetUpLists<D>>& lists, bool onDevice);
 
 private:
 	std::shared_ptr<HipMesh<D>> stack_;  // set for a stack member
@@ -279,28 +316,34 @@ private:
 	gcmx_ctx* ctx_ = nullptr;
 	int device;
 	real maximalEigenvalue = 0;
-	std::vector<GcmMatrices<D>> matrices;  // one per material condition
 	Models::T model_ = Models::T::ELASTIC;
-	std::vector<AcousticMatrices<D>> acousticMatrices;  // the same for an acoustic body
 	std::vector<real> deviceTau0_;
 	mutable std::vector<uint8_t> matIdAll_;
-	std::vector<int> materialNumbers_;
+	std::vector<int> materialNumbers_;  // one per material condition
 	bool pdeIsSetUp = false;
-	// set-up on the device: the ids wait on the device until a snapshot asks
-	void setUpPdeOnDevice(const Task& task);
-	void fetchMaterialIds() const;
-	/// This mesh's inner nodes as a box of its context, `offset` nodes along `axis`
-	/// (a stack member's place in the stack; axis < 0: none), with its own start.
-	gcmx_setup_box setupBox(int axis, int offset) const;
-	/// One table over the members' material conditions, bitwise-equal ones shared.
-	struct StackTable {
-		std::vector<const GcmMatrices<D>*> table;
-		std::vector<real> tau0;
-		std::vector<std::vector<int>> remap;  // [member][condition] -> table entry
+	void markSetUp();  // throws the second time
+	/// PLACEMENT.  A node of this mesh as a node of its context: a stack member
+	/// lies stackOffset_ nodes along stackAxis_.
+	IntD inContext(IntD it) const {
+		if (stack_) it[stackAxis_] += stackOffset_;
+		return it;
+	}
+	/// The box [boxMin, boxMax) of this mesh as a box of its context; throws
+	/// `refusal` where it leaves [-reach, size + reach) on an axis.
+	struct PlacedBox {
+		int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
 	};
-	static StackTable stackTable(const std::vector<const HostState<D>*>& states);
-	/// The used entries of a stack's table to the device; table entry -> device id or -1.
-	std::vector<int> setStackMaterials(const StackTable& t, const std::vector<int>& used);
+	PlacedBox placeBox(const IntD& boxMin, const IntD& boxMax, int reach, const char* refusal) const;
+	/// This mesh's inner nodes as a box of its context, with its own start.
+	gcmx_setup_box setupBox() const;
+	/// The used entries of a table to the device (gcmx_set_materials) and their
+	/// tau0 to deviceTau0_; entry -> device id, -1 for an unused one.
+	std::vector<int> sendMaterials(const MaterialTable<D>& table, const std::vector<int>& used);
+	struct NodePass;  // census() before the table is sent, place(dev) after
+	struct HostNodePass;
+	struct DeviceNodePass;
+	// set-up on the device: the ids wait on the device until a snapshot asks
+	void fetchMaterialIds() const;
 	mutable bool idsOnDevice_ = false;
 	std::vector<std::shared_ptr<Area>> materialAreas_;  // per condition, for fetchMaterialIds
 	std::vector<int> conditionOfDeviceId_;               // device id -> condition, -1: none, -2: several
