@@ -5,22 +5,29 @@ material sets.
 
 An entry knows how to build the oracle body (zero state: the caller fills it),
 how both sides advance, what both sides compare (all nodes, or the inner nodes
-where the one-pass face step keeps ghosts on the chip), and the kernel the
-profile must name, so that a case cannot drift onto another instance unnoticed.
+where the one-pass face step keeps ghosts on the chip and where the Maxwell ODE
+scales the stored stresses), and the kernel the profile must name, so that a
+case cannot drift onto another instance unnoticed.
 
 Both sides return, per step, the list of states to compare: one for a one-pass
 step, one per stage for the per-stage paths.  Each is a grid [X(, Y(, Z)), M]."""
+import copy
+
 import numpy as np
 
 from gcm_amd import PATH_GENERIC, PATH_SPLIT
+from tests import acoustic_ref
 from tests.helpers import context_for, oracle_body, random_materials
 from tests.test_gpu_2d import FACE2_CASES, face_body2, faces_at2
-from tests.test_gpu_faces import face_body, faces_at, free
+from tests.test_gpu_faces import conditions_at, face_body, face_maps, faces_at, free, partial_body
 from tests.test_gpu_ortho import H_A, ortho_body
 from tests.test_gpu_ortho_het import het_body
 from tests.test_gpu_wide_access import MATS, TAU_HET
 
 FREE_ALL = [(0, 0, free(0)), (1, 0, free(1)), (2, 0, free(2))]
+FREE_YZ = [(1, 0, free(1)), (2, 0, free(2))]
+H_ACOUSTIC = (0.5, 0.4, 0.3)
+TAU0, TAU0_HET = (3.0,), (3.0, 0.7)  # Maxwell relaxation times, per material
 
 
 def courant_tau(b, courant=0.9):
@@ -52,6 +59,26 @@ def _table2d(bs, sizes):
     return b
 
 
+def _acoustic(bs, sizes, h=H_ACOUSTIC):
+    """c = 2 and c rho = 3: no invariant V +- p / (c rho) of the impulse of
+    tests/states.py (V = 1, 2, 3 and p = 4) is zero, so it spreads both ways."""
+    return acoustic_ref.acoustic_body(3, bs, sizes, h=h, rho=1.5, lam=6.0)
+
+
+def _iso_het2(bs, sizes, conds=None):
+    """Two materials, random ids; `conds`: whole-face conditions (axis, side, values)."""
+    b = partial_body(bs, sizes, [(a, s, ("infinite",), v) for a, s, v in conds or ()], materials=MATS[:2])
+    random_materials(b, seed=sum(sizes) + bs)
+    return b
+
+
+def with_maxwell(body, tau0):
+    """`body` with MaxwellViscosityOde on, as Body.apply_odes expects it."""
+    assert len(tau0) == len(body.tables)
+    body.odes, body.tau0 = ["MAXWELL_VISCOSITY"], list(tau0)
+    return body
+
+
 MATERIAL_SETS = {
     "iso": (_iso, lambda b: 0.9),
     "iso_het": (_iso_het, lambda b: TAU_HET),
@@ -59,26 +86,45 @@ MATERIAL_SETS = {
     "ortho_het": (lambda bs, sizes: het_body(bs, sizes), courant_tau),
     "iso2d": (_iso2d, lambda b: 0.45),
     "table2d": (_table2d, lambda b: 0.45),
+    "acoustic": (_acoustic, courant_tau),
 }
 
 
 # ------------------------------------------------------------------ entries --
 
 class Launch:
-    """kind: "step" (gcmx_step, one pass), "faces" (gcmx_step_faces), "stages"
-    (gcmx_stage per axis on a forced path) or "slabs" (an in-process group)."""
+    """kind: "step" (gcmx_step, one pass), "faces" (gcmx_step_faces), "map"
+    (gcmx_step_face_map: the body's conditions as per-node face maps), "ode"
+    (gcmx_step_ode with `tau0` per material, whole-face conditions if `conds`;
+    the ODE must ride in the step's stores), "stages" (gcmx_stage per axis on a
+    forced path) or "slabs" (an in-process group).  `context`: the function that
+    builds the gcmx context of a body (the elastic one of tests/helpers.py)."""
 
     def __init__(self, name, kind, make_body, tau, prefix, marks=(), absent=(), fma_tag=False, compare="all",
-                 conds=None, faces_at=None, path=None, expect_path="fused", slabs=None):
+                 conds=None, faces_at=None, path=None, expect_path="fused", slabs=None, tau0=None,
+                 context=context_for):
         self.name, self.kind, self.make_body, self._tau = name, kind, make_body, tau
         self.prefix = (prefix,) if isinstance(prefix, str) else tuple(prefix)
         self.marks, self.absent, self.fma_tag = tuple(marks), tuple(absent), fma_tag
-        self.compare = "inner" if kind in ("faces", "slabs") else compare
+        self.compare = "inner" if kind in ("faces", "map", "ode", "slabs") else compare
         self.conds, self._faces_at, self.slabs = conds, faces_at, slabs
         self.path, self.expect_path = path, expect_path  # forced kernel path, gcmx_last_step_path
+        self.tau0, self.context = tau0, context
+        assert (kind == "ode") == (tau0 is not None)
+        self.has_faces = kind in ("faces", "map") or conds is not None
 
     def __repr__(self):
         return self.name
+
+    def variant(self, name, marks, absent=()):
+        """The same launch under another name, expected on another instance."""
+        e = copy.copy(self)
+        e.name, e.marks, e.absent = name, tuple(marks), tuple(absent)
+        return e
+
+    def faces(self, t):
+        """The gcmx_step_faces argument at time t (None: no conditions)."""
+        return self._faces_at(self.conds, t) if self.conds is not None else None
 
     def body(self):
         return self.make_body()
@@ -100,11 +146,14 @@ class Launch:
     def oracle_step(self, body, t):
         tau, out = self.tau(body), []
         for s in range(body.D):
-            if self.kind == "faces":
+            if self.has_faces:
                 body.apply_border(s, t)
             body.stage(s, tau)
             if self.kind == "stages":
                 out.append(self.grid(body, body.pde))
+        if self.kind == "ode":
+            assert body.odes and len(body.tau0) == len(self.tau0)
+            body.apply_odes(tau)
         if self.kind != "stages":
             out.append(self.grid(body, body.pde))
         return out
@@ -133,11 +182,12 @@ class Run:
         if launch.kind == "slabs":
             self.ctxs = self._slabs(body, launch.slabs)
         else:
-            self.ctxs = [context_for(body, path=launch.path)]
+            self.ctxs = [launch.context(body, path=launch.path)]
         for c in self.ctxs:
             c.fp_mode = fp
             c.profile(True)
         self.fp_fma = fp == gcm_amd.FP_FMA
+        self.fmap = self.ctxs[0].face_map(face_maps(body, body.sizes)) if launch.kind == "map" else None
 
     def _slabs(self, body, widths):
         """X slabs of `body` as one in-process group, boundary-first schedule; each
@@ -178,7 +228,12 @@ class Run:
         if L.kind == "slabs":
             self.G.local_group_steps(self.ctxs, self.tau, 1)
         elif L.kind == "faces":
-            c.step_faces(self.tau, L._faces_at(L.conds, t))
+            c.step_faces(self.tau, L.faces(t))
+        elif L.kind == "map":
+            c.step_face_map(self.tau, self.fmap, conditions_at(self.body, t))
+        elif L.kind == "ode":
+            c.step_ode(self.tau, list(L.tau0), faces=L.faces(t))
+            assert c.last_ode_fused, f"{L.name}: the ODE ran as a pass of its own"
         else:
             c.step(self.tau)
         for x in self.ctxs:
@@ -196,6 +251,8 @@ class Run:
         return names
 
     def close(self):
+        if self.fmap is not None:
+            self.fmap.close()
         for c in self.ctxs:
             c.close()
 
@@ -236,6 +293,43 @@ def _face2d():
                   (", FACES",), conds=conds, faces_at=faces_at2)
 
 
+def _faces3(name, bs, sizes, marks, conds=FREE_ALL, tau=0.9, make_body=None, prefix=None, absent=("!FACES",)):
+    """gcmx_step_faces with whole-face conditions (free surfaces on every face
+    unless `conds` says otherwise)."""
+    return Launch(name, "faces", make_body or (lambda: face_body(3, bs, sizes, conds)), tau,
+                  prefix or f"k_step_tx2<{bs}, ", marks, absent, fma_tag=True, conds=conds,
+                  faces_at=lambda c, t: faces_at(3, c, t))
+
+
+def _ode(name, bs, make_body, tau0, marks, tau=0.9, conds=None, absent=()):
+    """gcmx_step_ode, the ODE folded into the pass (asserted per step)."""
+    return Launch(name, "ode", lambda: with_maxwell(make_body(), tau0), tau, f"k_step_tx2<{bs}, ", marks, absent,
+                  fma_tag=True, tau0=tau0, conds=conds, faces_at=lambda c, t: faces_at(3, c, t))
+
+
+def _map(name, bs, sizes, conds, marks):
+    """gcmx_step_face_map; conds: (axis, side or 0, area, values) of partial_body."""
+    return Launch(name, "map", lambda: partial_body(bs, sizes, conds), 0.9, f"k_step_tx2<{bs}, ", marks, ("!FACES",),
+                  fma_tag=True)
+
+
+def _acoustic_launch(name, bs, sizes, zt, h=H_ACOUSTIC, tau=courant_tau, kf0="KF0"):
+    """The fp mode changes nothing on acoustic contexts: no FMA tag to expect."""
+    return Launch(name, "step", lambda: _acoustic(bs, sizes, h=h), tau, f"k_step_acoustic<{bs}, {zt}, {kf0}>",
+                  context=acoustic_ref.context_for)
+
+
+_zero = lambda t: 0.0
+# half of y- free, both z faces free on a box of x and y, no condition (zero
+# ghosts) on the rest of those faces and on every other face
+MAP_64 = [(1, -1, ("box", (-1, -1, -1), (2.5, 1, 100)), free(1)),
+          (2, 0, ("box", (0.5, 2.5, -100), (100, 8.5, 2000)), free(2))]
+# rows of 1024: partial y faces across the cut columns (z 508 .. 515), ending on
+# the cut, and on both parts; part of z+ held fixed in the last part
+MAP_1024 = [(1, -1, ("box", (-1, -1, 300.5), (100, 1, 700.5)), free(1)),
+            (1, 1, ("box", (1.5, 8, -1), (100, 100, 511.5)), free(1)),
+            (2, 1, ("box", (-1, 3.5, -100), (100, 7.5, 2000)), {"Vz": _zero, "Sxz": _zero})]
+
 CATALOG = [
     # ---- k_step_tx2
     _tx2("tx2-wide-bs2-4x5x64", 2, [4, 5, 64], "wide"),
@@ -254,6 +348,35 @@ CATALOG = [
     # takes (k_step_tx2's !KF0 instance at this border size; see the profile)
     Launch("courant15-bs2-4x6x64", "step", lambda: _iso(2, [4, 6, 64]), 1.5, ("k_step_tx2<2, ", "k_fused_xyz<2, "),
            ("!KF0",), fma_tag=True),
+    # ---- k_step_tx2 with faces beyond the UNI bs 2 instance; per-node face maps
+    _faces3("tx2-zs-faces-free6-bs2-4x12x1024", 2, [4, 12, 1024], (", UNI", ", FACES", ", ZS"),
+            prefix="k_step_tx2<2, 512, KF0, "),
+    _faces3("tx2-zs-faces-free6-bs1-4x8x1024", 1, [4, 8, 1024], (", UNI", ", FACES", ", ZS"),
+            prefix="k_step_tx2<1, 512, KF0, "),
+    _faces3("tx2-het-faces-free6-bs2-4x8x64", 2, [4, 8, 64], (", UNI", ", FACES", ", HET"), tau=TAU_HET,
+            make_body=lambda: _iso_het2(2, [4, 8, 64], FREE_ALL)),
+    _faces3("tx2-faces-!uni-free6-bs2-4x8x40", 2, [4, 8, 40], ("!UNI", ", FACES")),
+    _faces3("tx2-faces-free6-bs1-4x6x64", 1, [4, 6, 64], (", FACES",)),
+    # floor(q) = 1 on the fast waves, y and z faces free (no x face: the x ghosts
+    # are the state's own)
+    _faces3("tx2-faces-courant15-bs2-4x8x64", 2, [4, 8, 64], ("!KF0", ", FACES"), conds=FREE_YZ, tau=1.5),
+    _map("tx2-map-bs2-6x12x64", 2, [6, 12, 64], MAP_64, (", FACES",)),
+    _map("tx2-map-zs-bs2-4x10x1024", 2, [4, 10, 1024], MAP_1024, (", FACES", ", ZS")),
+    # ---- the Maxwell ODE folded into the pass: one factor, per-node factors, with
+    # faces, and in both kernels of the z split
+    _ode("tx2-ode-bs2-4x6x64", 2, lambda: _iso(2, [4, 6, 64]), TAU0, ("<2, 64, ",)),
+    _ode("tx2-het-ode-bs1-5x7x64", 1, lambda: _iso_het2(1, [5, 7, 64]), TAU0_HET, (", HET",), tau=TAU_HET),
+    _ode("tx2-faces-ode-bs2-4x8x64", 2, lambda: face_body(3, 2, [4, 8, 64], FREE_ALL), TAU0, (", UNI", ", FACES"),
+         conds=FREE_ALL, absent=("!FACES", ", N8")),
+    _ode("tx2-zs-ode-bs2-4x12x1024", 2, lambda: _iso(2, [4, 12, 1024]), TAU0, (", UNI", ", ZS")),
+    # ---- k_step_acoustic (M = D + 1; its own stage code and limiter)
+    _acoustic_launch("acoustic-bs2-4x5x64", 2, [4, 5, 64], 64),
+    _acoustic_launch("acoustic-bs1-6x9x37", 1, [6, 9, 37], 64),
+    _acoustic_launch("acoustic-bs3-5x7x20", 3, [5, 7, 20], 64),
+    # floor(q) = 1: tau = h / c (c = 2), Courant 1 on a unit grid
+    _acoustic_launch("acoustic-!kf0-bs2-6x9x37", 2, [6, 9, 37], 64, h=(1.0, 1.0, 1.0), tau=0.5, kf0="!KF0"),
+    # rows with a wave seam and idle lanes
+    _acoustic_launch("acoustic-bs2-3x5x130", 2, [3, 5, 130], 256),
     # ---- other 3-D paths
     Launch("fused_xyz-bs3-4x7x100", "step", lambda: _iso(3, [4, 7, 100]), 0.9, "k_fused_xyz<3, ", fma_tag=True),
     _stages("split-bs2-9x4x300", [9, 4, 300], "split"),

@@ -1,6 +1,7 @@
 """Deterministic states the random parity data never produces: a lone impulse
 in a quiescent medium, piecewise-constant blocks (equal neighbours, exactly zero
-differences, a jump at every cut), a linear ramp (second differences exactly
+differences, a jump at every cut; for rows longer than 512 also with the last
+cut on the part cut), a linear ramp (second differences exactly
 zero) and the random state scaled by a power of two far from 1 (subnormals
 included).  Every family fills the inner nodes only: ghosts stay zero, so the
 one-pass paths stay eligible."""
@@ -13,6 +14,9 @@ SCALES = (-1000, 1000, -1060)
 def _inner(body):
     body.pde[:] = 0.0
     return body.inner_view()
+
+
+Z_PART = 512  # rows longer than this run as parts of Z_PART lanes, cut at every multiple
 
 
 def z_cut(body):
@@ -29,6 +33,12 @@ def impulse_nodes(body):
     if body.D == 3 and n[2] >= 128:
         out["z63"] = centre[:2] + (63,)
         out["z64"] = centre[:2] + (64,)
+    if body.D == 3 and n[2] > Z_PART:
+        # both sides of the part cut, and the columns that at borderSize 2 lie just
+        # outside the 2 bs columns the seam kernel stores (510 .. 513): the parts
+        # store them, the seam kernel's group of 4 bs columns reads them
+        for z in (Z_PART - 1, Z_PART, Z_PART - 3, Z_PART + 2):
+            out[f"z{z}"] = centre[:2] + (z,)
     return out
 
 
@@ -40,13 +50,13 @@ def impulse(body, where="centre"):
     return node
 
 
-def steps(body):
-    """Piecewise constant over the 2^D blocks cut at X // 2, Y // 2 and z_cut; the
-    value of block o and component c is STEP_VALUES[(o + (o >> 2) + c) % 4], which
-    differs across every cut."""
+def steps(body, last_cut=None):
+    """Piecewise constant over the 2^D blocks cut at X // 2, Y // 2 and z_cut (or
+    `last_cut`); the value of block o and component c is
+    STEP_VALUES[(o + (o >> 2) + c) % 4], which differs across every cut."""
     v = _inner(body)
     D = body.D
-    cuts = [body.sizes[i] // 2 for i in range(D - 1)] + [z_cut(body)]
+    cuts = [body.sizes[i] // 2 for i in range(D - 1)] + [z_cut(body) if last_cut is None else last_cut]
     o = np.zeros(v.shape[:D], dtype=np.int64)
     for i in range(D):
         shape = [1] * D
@@ -55,6 +65,13 @@ def steps(body):
     vals = np.array(STEP_VALUES)
     for c in range(body.M):
         v[..., c] = vals[(o + (o >> 2) + c) % 4]
+
+
+def steps_zcut(body):
+    """`steps` with the last cut on the part cut of rows longer than Z_PART: the
+    jump and the limiter ties lie on the columns the seam kernel recomputes."""
+    assert body.D == 3 and body.sizes[2] > Z_PART
+    steps(body, last_cut=Z_PART)
 
 
 def ramp(body):

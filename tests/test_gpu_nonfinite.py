@@ -1,7 +1,8 @@
 """Non-finite input: where a NaN or an Inf may go.
 
 The random state with one inner node tainted (the centre; for rows of 128 and
-more also the node at z = 63, next to the wave seam), one step, exact build.
+more also the node at z = 63, next to the wave seam; for rows longer than 512
+also the node at z = 511, next to the part cut), one step, exact build.
 R is the set of nodes where the oracle's result has a non-finite component.
 
   1. Outside R the GPU result is finite and equals the oracle bit for bit.  The
@@ -16,7 +17,8 @@ R is the set of nodes where the oracle's result has a non-finite component.
   3. The one-pass kernel and the generic stages need not agree inside R.
 
 tests/test_states_cpu.py asserts the oracle fact this rests on: R is the
-(2 bs + 1)^3 box around the tainted node, clipped to the grid, all components."""
+(2 bs + 1)^3 box around the tainted node, clipped to the grid, all components
+(the acoustic medium's R is stated there too)."""
 import numpy as np
 import pytest
 
@@ -39,7 +41,7 @@ def G():
 
 def taint_nodes(body):
     nodes = states.impulse_nodes(body)
-    return [nodes[k] for k in ("centre", "z63") if k in nodes]
+    return [nodes[k] for k in ("centre", "z63", "z511") if k in nodes]
 
 
 @pytest.mark.parametrize("variant", VARIANTS)

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from tests import rawlayer, states
-from tests.launch_catalog import BY_NAME, CATALOG, Launch
+from tests.launch_catalog import BY_NAME, CATALOG
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +31,8 @@ EVEN_PADS = {"GCMX_ROW_PAD": "16", "GCMX_PLANE_PAD": "64"}
 # the odd pads put k_step_tx2's UNI launches on the 8-byte path (", N8"), as
 # test_odd_strides_take_the_narrow_path shows; the even ones keep the wide path
 PADDED = [("tx2-wide-bs2-4x5x64", "odd"), ("tx2-!uni-bs2-4x6x40", "odd"), ("ortho-bs2-6x9x37", "odd"),
-          ("2d-iso-bs2-21x70", "odd"), ("tx2-wide-bs2-4x5x64", "even")]
+          ("2d-iso-bs2-21x70", "odd"), ("tx2-wide-bs2-4x5x64", "even"), ("acoustic-bs2-4x5x64", "odd"),
+          ("tx2-faces-ode-bs2-4x8x64", "odd")]
 
 
 @pytest.fixture(scope="module")
@@ -101,9 +102,9 @@ def test_padding_with_perturbed_strides(G, monkeypatch, name, pads, fp):
     for k, v in (ODD_PADS if pads == "odd" else EVEN_PADS).items():
         monkeypatch.setenv(k, v)
     entry = BY_NAME[name]
-    if pads == "odd" and name.startswith("tx2-wide"):
+    if pads == "odd" and ", N8" in entry.absent:
         # rows at odd elements: the same launch on the UNI instance's 8-byte path
-        entry = Launch(name + "-odd", entry.kind, entry.make_body, 0.9, entry.prefix, (", UNI", ", N8"), fma_tag=True)
+        entry = entry.variant(name + "-odd", entry.marks + (", N8",), tuple(m for m in entry.absent if m != ", N8"))
     dim = entry.body().D
     c = G.Context(dim, 2, [4] * dim)
     g = c.geometry()
@@ -116,12 +117,14 @@ def test_padding_with_perturbed_strides(G, monkeypatch, name, pads, fp):
 
 
 @pytest.mark.parametrize("name", ["tx2-wide-bs2-4x5x64", "tx2-wide-bs1-4x5x64", "tx2-!uni-bs2-4x6x40",
-                                  "tx2-zs-bs2-4x12x1024", "ortho-bs2-6x9x37", "2d-iso-bs2-21x70"])
+                                  "tx2-zs-bs2-4x12x1024", "ortho-bs2-6x9x37", "2d-iso-bs2-21x70",
+                                  "acoustic-bs2-4x5x64", "tx2-faces-courant15-bs2-4x8x64", "tx2-ode-bs2-4x6x64"])
 def test_a_value_read_for_a_ghost_is_noticed(G, name):
     """The pair has teeth: the sentinel in ONE element the step does read for a
     ghost (the x ghost next to a central inner node, component 0; the y and z
-    ghosts of the state a step starts from are read by no stage) changes the
-    result, as it would read from a pad."""
+    ghosts of the state a step starts from are read by no stage; the face entry
+    has no condition on its x faces, whose fill would overwrite the ghost) changes
+    the result, as it would read from a pad."""
     entry = BY_NAME[name]
     body = entry.body()
     states.uniform(body, seed=7)
@@ -135,7 +138,8 @@ def test_a_value_read_for_a_ghost_is_noticed(G, name):
         raw[e] = rawlayer.SENTINEL
         rawlayer.write_layer(c, w, raw)
     a, b = clean.step(0.0)[-1], dirty.step(0.0)[-1]
-    inner = tuple(slice(c.bs, -c.bs) for _ in c.sizes)
+    # the inner nodes of an all-nodes grid; a face or ODE entry returns them alone
+    inner = tuple(slice(c.bs, -c.bs) for _ in c.sizes) if entry.compare == "all" else ()
     assert not np.array_equal(a[inner], b[inner]), f"{name}: a sentinel in the ghost {ghost} left the result unchanged"
     clean.close()
     dirty.close()

@@ -1,8 +1,10 @@
 """Every catalogue launch (tests/launch_catalog.py) on the structured states of
 tests/states.py: a lone impulse (at the centre, in the first and the last inner
-node, and on both sides of the wave seam of long rows), piecewise-constant
-blocks, a linear ramp, and the random state scaled by 2^-1000, 2^1000 and
-2^-1060.  Two steps each.
+node, on both sides of the wave seam of long rows, and for rows longer than 512
+on both sides of the part cut and in the columns next to those the seam kernel
+stores), piecewise-constant blocks (for rows longer than 512 also with the jump
+on the part cut), a linear ramp, and the random state scaled by 2^-1000, 2^1000
+and 2^-1060.  Two steps each.
 
 Exact build: no non-finite value on either side, and equal to the oracle with
 +0 and -0 identified: (got + 0.0) and (want + 0.0) have the
@@ -25,8 +27,8 @@ pytestmark = pytest.mark.gpu
 
 STEPS = 2
 TOL = 1e-10
-PLACEMENTS = ("centre", "first", "last", "z63", "z64")
-FAMILIES = tuple(f"impulse-{p}" for p in PLACEMENTS) + ("steps", "ramp")
+PLACEMENTS = ("centre", "first", "last", "z63", "z64", "z509", "z511", "z512", "z514")
+FAMILIES = tuple(f"impulse-{p}" for p in PLACEMENTS) + ("steps", "steps-zcut", "ramp")
 
 
 @pytest.fixture(scope="module")
@@ -39,13 +41,17 @@ def G():
 def fill(body, family):
     if family.startswith("impulse-"):
         return states.impulse(body, family[len("impulse-"):])
-    {"steps": states.steps, "ramp": states.ramp, "uniform": states.uniform}[family](body)
+    {"steps": states.steps, "steps-zcut": states.steps_zcut, "ramp": states.ramp,
+     "uniform": states.uniform}[family](body)
 
 
-# rows shorter than 128 have no wave seam: nothing to place there
+# rows shorter than 128 have no wave seam, rows up to 512 no part cut: nothing
+# to place there
 _PLACED = {e.name: set(states.impulse_nodes(e.body())) for e in CATALOG}
+_ZCUT = {e.name for e in CATALOG if e.body().D == 3 and e.body().sizes[2] > states.Z_PART}
 CASES = [(e, f) for e in CATALOG for f in FAMILIES
-         if not f.startswith("impulse-") or f[len("impulse-"):] in _PLACED[e.name]]
+         if (f[len("impulse-"):] in _PLACED[e.name] if f.startswith("impulse-")
+             else f != "steps-zcut" or e.name in _ZCUT)]
 
 
 def run_oracle(entry, fill_body):
