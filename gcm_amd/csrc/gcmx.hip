@@ -202,6 +202,23 @@ struct gcmx_ctx {
 	void* setup_d = nullptr;
 	// bytes the layer and observation calls copied (gcmx_transfer_stats)
 	uint64_t bytes_d2h = 0, bytes_h2d = 0;
+	// the recorders created on this context (gcmx_destroy detaches them)
+	std::vector<gcmx_recorder*> recorders;
+};
+
+// Receivers of a context and the device buffer of their samples
+// (gcmx_recorder_create*): offsets [n][K] and weights [n][K] (K = 1: a node
+// recorder, no weights), slot s at element s * n_q * n, [q][i] inside.
+struct gcmx_recorder {
+	gcmx_ctx* ctx = nullptr;  // null once the context is destroyed (detached)
+	int device = 0;
+	long long n = 0;
+	int K = 1;
+	ObserveQ oq{};
+	int capacity = 0, count = 0;
+	long long* off_d = nullptr;
+	double* w_d = nullptr;
+	double* buf_d = nullptr;
 };
 
 // Inner nodes of a context as element offsets of its layout (gcmx_node_list_create).
@@ -1414,6 +1431,10 @@ void gcmx_destroy(gcmx_ctx* c) {
 	if (c->inner_stream) (void)hipStreamSynchronize(c->inner_stream);
 	if (c->bnd_stream) (void)hipStreamSynchronize(c->bnd_stream);
 	drain_timings(c);
+	// the stream's records are done: the recorders keep their samples, readable
+	// without the context
+	for (gcmx_recorder* r : c->recorders) r->ctx = nullptr;
+	c->recorders.clear();
 	for (hipEvent_t ev : c->event_pool) (void)hipEventDestroy(ev);
 	if (c->probe_stream) (void)hipStreamSynchronize(c->probe_stream);
 	if (c->comm) {  // non-blocking communicator: finalize (bounded), then destroy; abort on failure
@@ -2032,6 +2053,151 @@ gcmx_status gcmx_gather(gcmx_ctx* c, const gcmx_node_list* h, int n_q, const int
 	}
 	if ((s = wait_stream(c, c->stream, "gcmx_gather")) != GCMX_OK) return s;
 	return observe_fetch(c, out, 0, bytes);
+}
+
+// ---- recorders: samples kept on the device, read in batches ------------------------
+
+namespace {
+
+// A recorder of `n` receivers with K offsets (and, K > 1, weights) each, taken
+// from the host (off_h, w_h) or, a node list's, from the device (off_src_d).
+// Nothing is left behind on failure.
+gcmx_status recorder_make(gcmx_ctx* c, long long n, int K, const long long* off_h, const long long* off_src_d,
+                          const double* w_h, const ObserveQ& oq, int capacity, gcmx_recorder** out) {
+	size_t slot = 0, elems = 0, bytes = 0;
+	if (__builtin_mul_overflow((size_t)n, (size_t)oq.n, &slot) || __builtin_mul_overflow(slot, (size_t)capacity, &elems) ||
+	    __builtin_mul_overflow(elems, sizeof(double), &bytes))
+		return fail(GCMX_ERR_OOM, "recorder buffer larger than the address space");
+	auto* r = new gcmx_recorder();
+	r->ctx = c;
+	r->device = c->device;
+	r->n = n;
+	r->K = K;
+	r->oq = oq;
+	r->capacity = capacity;
+	const size_t off_bytes = (size_t)n * K * sizeof(long long), w_bytes = K > 1 ? (size_t)n * K * sizeof(double) : 0;
+	auto drop = [&](gcmx_status s, const char* msg) {
+		(void)hipGetLastError();
+		(void)hipFree(r->off_d);
+		(void)hipFree(r->w_d);
+		(void)hipFree(r->buf_d);
+		delete r;
+		return fail(s, msg);
+	};
+	if (hipMalloc(&r->buf_d, bytes) != hipSuccess) return drop(GCMX_ERR_OOM, "recorder buffer allocation failed");
+	if (hipMalloc(&r->off_d, off_bytes) != hipSuccess) return drop(GCMX_ERR_OOM, "device allocation failed");
+	if (w_bytes && hipMalloc(&r->w_d, w_bytes) != hipSuccess) return drop(GCMX_ERR_OOM, "device allocation failed");
+	if (hipMemcpy(r->off_d, off_h ? off_h : off_src_d, off_bytes, off_h ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) !=
+	    hipSuccess)
+		return drop(GCMX_ERR_HIP, "receiver upload failed");
+	if (w_bytes && hipMemcpy(r->w_d, w_h, w_bytes, hipMemcpyHostToDevice) != hipSuccess)
+		return drop(GCMX_ERR_HIP, "receiver upload failed");
+	if (off_h) c->bytes_h2d += off_bytes + w_bytes;
+	c->recorders.push_back(r);
+	*out = r;
+	return GCMX_OK;
+}
+
+}  // namespace
+
+gcmx_status gcmx_recorder_create(gcmx_ctx* c, const gcmx_node_list* h, int n_q, const int* qs, int capacity,
+                                 gcmx_recorder** out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	*out = nullptr;
+	if (!h || h->ctx != c) return fail(GCMX_ERR_INVALID_ARG, "node list of another context");
+	if (capacity < 1) return fail(GCMX_ERR_INVALID_ARG, "a recorder holds at least one sample");
+	ObserveQ oq;
+	if ((s = observe_q(c, n_q, qs, 1, oq)) != GCMX_OK) return s;
+	// the copy: the list may be destroyed afterwards
+	return recorder_make(c, h->n, 1, nullptr, h->off_d, nullptr, oq, capacity, out);
+}
+
+gcmx_status gcmx_recorder_create_points(gcmx_ctx* c, int n_points, const double* positions, int n_q, const int* qs,
+                                        int capacity, gcmx_recorder** out) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	*out = nullptr;
+	if (n_points < 1 || !positions) return fail(GCMX_ERR_INVALID_ARG, "a recorder needs at least one point");
+	if (capacity < 1) return fail(GCMX_ERR_INVALID_ARG, "a recorder holds at least one sample");
+	ObserveQ oq;
+	if ((s = observe_q(c, n_q, qs, 1, oq)) != GCMX_OK) return s;
+	const int D = c->D, K = 1 << D;
+	std::vector<long long> off((size_t)n_points * K);
+	std::vector<double> w((size_t)n_points * K);
+	for (int i = 0; i < n_points; i++) {
+		int base[3];
+		double wk[8];
+		if (!receiver_corners(D, c->geo.sizes, positions + (size_t)i * D, base, wk))
+			return fail(GCMX_ERR_INVALID_ARG,
+			            "a point needs 0 <= position <= size - 1 on every axis, and at least two nodes per axis");
+		for (int k = 0; k < K; k++) {
+			int it[3] = {0, 0, 0};
+			for (int d = 0; d < D; d++) it[d] = base[d] + receiver_corner_bit(D, k, d);
+			off[(size_t)i * K + k] = dev_offset(c->geo, it);
+			w[(size_t)i * K + k] = wk[k];
+		}
+	}
+	return recorder_make(c, n_points, K, off.data(), nullptr, w.data(), oq, capacity, out);
+}
+
+void gcmx_recorder_destroy(gcmx_recorder* r) {
+	if (!r) return;
+	(void)hipSetDevice(r->device);
+	if (r->ctx) {
+		auto& v = r->ctx->recorders;
+		v.erase(std::remove(v.begin(), v.end(), r), v.end());
+	}
+	// hipFree waits for the device, so a record that still writes the buffer is done
+	(void)hipFree(r->off_d);
+	(void)hipFree(r->w_d);
+	(void)hipFree(r->buf_d);
+	delete r;
+}
+
+gcmx_status gcmx_record(gcmx_ctx* c, gcmx_recorder* r) {
+	gcmx_status s = check_ctx(c);
+	if (s) return s;
+	if (!r || r->ctx != c) return fail(GCMX_ERR_INVALID_ARG, "recorder of another context, or detached");
+	if (r->count == r->capacity) return fail(GCMX_ERR_STATE, "the recorder is full: read and reset it");
+	// no halo_wait: an exchange writes ghost planes, a receiver reads inner nodes
+	const size_t slot = (size_t)r->n * r->oq.n;
+	{
+		Timed t(c, "record_q", (double)slot * sizeof(double) * (r->K + 1), c->stream);
+		launch_record(c->cur, c->geo, r->n, r->K, r->off_d, r->w_d, r->oq, r->buf_d + (size_t)r->count * slot, c->stream);
+		HIP_TRY(hipGetLastError());
+	}
+	r->count++;
+	return GCMX_OK;
+}
+
+int gcmx_recorder_count(const gcmx_recorder* r) { return r ? r->count : 0; }
+
+gcmx_status gcmx_recorder_read(gcmx_recorder* r, int first, int count, double* out) {
+	if (!r) return fail(GCMX_ERR_INVALID_ARG, "null recorder");
+	if (!out) return fail(GCMX_ERR_INVALID_ARG, "null output");
+	if (first < 0 || count < 1 || (long long)first + count > r->count)
+		return fail(GCMX_ERR_INVALID_ARG, "samples outside those the recorder holds");
+	gcmx_ctx* c = r->ctx;
+	if (c) {
+		gcmx_status s = check_ctx(c);
+		if (s) return s;
+		if ((s = wait_stream(c, c->stream, "gcmx_recorder_read")) != GCMX_OK) return s;
+	} else if (hipSetDevice(r->device) != hipSuccess) {  // detached: gcmx_destroy waited for the records
+		return fail(GCMX_ERR_HIP, "hipSetDevice failed");
+	}
+	const size_t slot = (size_t)r->n * r->oq.n, bytes = (size_t)count * slot * sizeof(double);
+	HIP_TRY(hipMemcpy(out, r->buf_d + (size_t)first * slot, bytes, hipMemcpyDeviceToHost));
+	if (c) c->bytes_d2h += bytes;
+	return GCMX_OK;
+}
+
+gcmx_status gcmx_recorder_reset(gcmx_recorder* r) {
+	if (!r) return fail(GCMX_ERR_INVALID_ARG, "null recorder");
+	r->count = 0;
+	return GCMX_OK;
 }
 
 namespace {

@@ -42,6 +42,30 @@ __global__ __launch_bounds__(256) void k_gather_q(const double* __restrict__ cur
 	out[i] = observe_value<false>(cur, cs, off[node], oq.comp[k], oq);
 }
 
+// One thread per (receiver, quantity); latency-bound like k_gather_q.  K == 1 (a
+// node recorder) stores observe_value itself, no multiply: the sample is bitwise
+// k_gather_q's, the sign of zero and NaN payloads included.  K = 2^dim (a point
+// recorder) blends the corners in ascending order, every product and sum rounded
+// on its own (this file has the one exact build).
+__global__ __launch_bounds__(256) void k_record(const double* __restrict__ cur, long long cs, long long n, int K,
+                                                const long long* __restrict__ off, const double* __restrict__ wt,
+                                                ObserveQ oq, double* __restrict__ out) {
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n * oq.n) return;
+	const int q = (int)(i / n);
+	const long long r = i - (long long)q * n;
+	const int comp = oq.comp[q];
+	if (K == 1) {
+		out[i] = observe_value<false>(cur, cs, off[r], comp, oq);
+		return;
+	}
+	const long long* __restrict__ o = off + r * K;
+	const double* __restrict__ w = wt + r * K;
+	double acc = w[0] * observe_value<false>(cur, cs, o[0], comp, oq);
+	for (int k = 1; k < K; k++) acc = acc + w[k] * observe_value<false>(cur, cs, o[k], comp, oq);
+	out[i] = acc;
+}
+
 // The box of k_pack_vtk on the axes A (x: the VTK order's fastest), B (3-D: y) and
 // F (the layer's fastest: z in 3-D, y in 2-D, stride 1).
 // A strided launch (every stride-th node per axis) describes its lattice of
@@ -259,6 +283,14 @@ void launch_gather_q(const double* cur, const Geo& g, long long n, const long lo
 	if (total <= 0) return;
 	hipLaunchKernelGGL(k_gather_q, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, cur, g.cs, n, off_d, oq,
 	                   out_d);
+}
+
+void launch_record(const double* cur, const Geo& g, long long n, int K, const long long* off_d, const double* w_d,
+                   const ObserveQ& oq, double* out_d, hipStream_t st) {
+	const long long total = n * oq.n;
+	if (total <= 0) return;
+	hipLaunchKernelGGL(k_record, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, cur, g.cs, n, K, off_d, w_d,
+	                   oq, out_d);
 }
 
 void launch_pack_vtk(const double* cur, const Geo& g, const int bmin[3], const int bmax[3], float* vel_d,

@@ -50,6 +50,8 @@ SYMBOLS = [
     "gcmx_upload", "gcmx_download", "gcmx_read_box", "gcmx_write_box", "gcmx_fill_random",
     "gcmx_setup_state", "gcmx_setup_census", "gcmx_setup_material_ids", "gcmx_download_material_ids",
     "gcmx_node_list_create", "gcmx_node_list_destroy", "gcmx_gather", "gcmx_snapshot_box", "gcmx_snapshot_strided", "gcmx_scan",
+    "gcmx_recorder_create", "gcmx_recorder_create_points", "gcmx_recorder_destroy", "gcmx_record",
+    "gcmx_recorder_count", "gcmx_recorder_read", "gcmx_recorder_reset",
     "gcmx_transfer_stats",
     "gcmx_stage", "gcmx_step",
     "gcmx_set_kernel_path", "gcmx_set_step_schedule", "gcmx_set_fp_mode", "gcmx_get_fp_mode", "gcmx_effective_path", "gcmx_last_step_path",
@@ -212,6 +214,18 @@ def lib() -> ctypes.CDLL:
         fp = ctypes.POINTER(ctypes.c_float)
         L.gcmx_snapshot_strided.argtypes = [vp, ip, ip, ip, ctypes.c_int, ctypes.c_int, ip, fp, fp]
         L.gcmx_transfer_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    # (the recorders: bound when present, like the observation calls)
+    if hasattr(L, "gcmx_record"):
+        L.gcmx_recorder_create.argtypes = [vp, vp, ctypes.c_int, ip, ctypes.c_int, ctypes.POINTER(vp)]
+        L.gcmx_recorder_create_points.argtypes = [vp, ctypes.c_int, dp, ctypes.c_int, ip, ctypes.c_int,
+                                                  ctypes.POINTER(vp)]
+        L.gcmx_recorder_destroy.argtypes = [vp]
+        L.gcmx_recorder_destroy.restype = None
+        L.gcmx_record.argtypes = [vp, vp]
+        L.gcmx_recorder_count.argtypes = [vp]
+        L.gcmx_recorder_count.restype = ctypes.c_int
+        L.gcmx_recorder_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
+        L.gcmx_recorder_reset.argtypes = [vp]
     L.gcmx_stage.argtypes = [vp, ctypes.c_int, ctypes.c_double]
     L.gcmx_step.argtypes = [vp, ctypes.c_double]
     L.gcmx_set_kernel_path.argtypes = [vp, ctypes.c_int]
@@ -488,6 +502,21 @@ class Context:
         out = np.empty((len(quantities), node_list.n))
         _check(lib().gcmx_gather(self._ptr, node_list.ptr, len(quantities), _ip(quantities), _dp(out)))
         return out
+
+    def recorder(self, node_list: "NodeList", quantities: Sequence[int], capacity: int) -> "Recorder":
+        """gcmx_recorder_create: a device buffer of `capacity` samples of the
+        quantities at the list's nodes (the list is copied)."""
+        return Recorder(self, quantities, capacity, node_list=node_list)
+
+    def point_recorder(self, positions: np.ndarray, quantities: Sequence[int], capacity: int) -> "Recorder":
+        """gcmx_recorder_create_points: receivers at positions [n, dim] in inner-index
+        units, blended from the 2^dim nodes around each."""
+        return Recorder(self, quantities, capacity, positions=positions)
+
+    def record(self, rec: "Recorder"):
+        """gcmx_record: the current layer's sample into the recorder, on the stream
+        (no host wait, no copy)."""
+        _check(lib().gcmx_record(self._ptr, rec.ptr))
 
     def snapshot_box(self, box_min: Sequence[int], box_max: Sequence[int], quantities: Sequence[int],
                      velocity: bool = True):
@@ -826,6 +855,53 @@ class NodeList:
     def close(self):
         if self.ptr and self.ptr.value:
             lib().gcmx_node_list_destroy(self.ptr)
+        self.ptr = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Recorder:
+    """gcmx_recorder: samples of quantities at receivers (nodes, or points between
+    nodes), appended on the device by Context.record and read in batches.  It
+    outlives its context: after Context.close the samples stay readable."""
+
+    def __init__(self, ctx: Context, quantities: Sequence[int], capacity: int, node_list=None, positions=None):
+        self.ptr = ctypes.c_void_p()
+        self.n_q = len(quantities)
+        if node_list is not None:
+            self.n = node_list.n
+            _check(lib().gcmx_recorder_create(ctx.ptr, node_list.ptr, self.n_q, _ip(quantities), int(capacity),
+                                              ctypes.byref(self.ptr)))
+        else:
+            positions = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, ctx.dim)
+            self.n = positions.shape[0]
+            _check(lib().gcmx_recorder_create_points(ctx.ptr, self.n, _dp(positions), self.n_q, _ip(quantities),
+                                                     int(capacity), ctypes.byref(self.ptr)))
+
+    @property
+    def count(self) -> int:
+        """Samples held."""
+        return int(lib().gcmx_recorder_count(self.ptr))
+
+    def read(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """gcmx_recorder_read: samples first ... first + count - 1 (default: all from
+        `first`) as [count, n_q, n] float64."""
+        if count is None:
+            count = self.count - first
+        out = np.empty((max(0, int(count)), self.n_q, self.n))
+        _check(lib().gcmx_recorder_read(self.ptr, int(first), int(count), _dp(out)))
+        return out
+
+    def reset(self):
+        _check(lib().gcmx_recorder_reset(self.ptr))
+
+    def close(self):
+        if self.ptr and self.ptr.value:
+            lib().gcmx_recorder_destroy(self.ptr)
         self.ptr = ctypes.c_void_p()
 
     def __del__(self):

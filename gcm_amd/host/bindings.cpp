@@ -509,6 +509,38 @@ PYBIND11_MODULE(_gcm_host, m) {
 		         t.detector.area = makeArea(area);
 		         t.detector.gridId = gridId;
 	         })
+	    .def("set_detector_buffer",
+	         [](Task& t, int n) {
+		         if (n < 0) throw Exception("set_detector_buffer: at least 0 snapshots");
+		         t.detector.bufferSteps = n;
+	         },
+	         py::arg("n"),
+	         "the cubic SliceSnapshotter keeps n snapshots on the device between two writes of its files (0: none, "
+	         "every snapshot waits for the device)")
+	    .def("set_receivers",
+	         [](Task& t, const std::vector<std::vector<real>>& points, std::vector<std::string> qs, size_t gridId,
+	            int bufferSteps) {
+		         if (points.empty()) throw Exception("set_receivers: at least one point");
+		         if (qs.empty() || qs.size() > GCMX_MAX_BORDER_Q) throw Exception("set_receivers: 1 to 16 quantities");
+		         if (bufferSteps < 1) throw Exception("set_receivers: buffer_steps is at least 1");
+		         Task::Receivers r;
+		         for (const auto& p : points) {
+			         if (p.empty() || p.size() > 3) throw Exception("set_receivers: one coordinate per axis");
+			         Real3 x = {0, 0, 0};
+			         for (size_t i = 0; i < p.size(); i++) {
+				         if (!std::isfinite(p[i])) throw Exception("set_receivers: a coordinate is not finite");
+				         x[i] = p[i];
+			         }
+			         r.points.push_back(x);
+		         }
+		         for (auto& q : qs) r.quantities.push_back(quantity(q));
+		         r.gridId = gridId;
+		         r.bufferSteps = bufferSteps;
+		         t.receivers = r;
+	         },
+	         py::arg("points"), py::arg("quantities"), py::arg("grid_id") = 0, py::arg("buffer_steps") = 256,
+	         "receivers of the DETECTOR snapshotter: points in physical coordinates inside body grid_id, one sample "
+	         "per snapshot step, one text file per buffer_steps samples")
 	    .def_property("grid", [](Task& t) {
 		                  return std::string(t.globalSettings.gridId == Grids::T::SIMPLEX ? "SIMPLEX" : "CUBIC");
 	                  },

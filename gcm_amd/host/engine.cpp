@@ -66,6 +66,7 @@ void AbstractEngine::run() {
 		writeSnapshots(step);
 		if (!file.empty() && step % checkpoint.stepsPerCheckpoint == 0) saveState(file);
 	}
+	flushSnapshots();
 }
 
 void AbstractEngine::runSteps(int n) {
@@ -766,6 +767,61 @@ std::vector<real> HipMesh<D>::gather(const NodeList& nodes, const std::vector<in
 }
 
 template <int D>
+std::shared_ptr<typename HipMesh<D>::Recorder> HipMesh<D>::recorder(const std::vector<IntD>& nodes,
+                                                                    const std::vector<int>& quantities,
+                                                                    int capacity) const {
+	const std::shared_ptr<NodeList> list = nodeList(nodes);  // copied by the recorder
+	auto rec = std::make_shared<Recorder>();
+	gcmxCheck(gcmx_recorder_create(ctx_, list->handle, (int)quantities.size(), quantities.data(), capacity, &rec->handle),
+	          "gcmx_recorder_create");
+	rec->receivers = nodes.size();
+	rec->quantities = quantities.size();
+	return rec;
+}
+
+template <int D>
+std::shared_ptr<typename HipMesh<D>::Recorder> HipMesh<D>::recorder(const std::vector<std::array<real, D>>& points,
+                                                                    const std::vector<int>& quantities,
+                                                                    int capacity) const {
+	std::vector<double> flat;
+	flat.reserve(points.size() * D);
+	for (const auto& pos : points) {
+		// this mesh's inner nodes first (a stack member's neighbours are inner nodes
+		// of the context too), then the place in the context
+		IntD lo{}, hi{};
+		for (int d = 0; d < D; d++) {
+			if (!(pos[d] >= 0 && pos[d] <= (real)(this->sizes[d] - 1)))
+				throw Exception("recorder: a point outside the inner nodes of the mesh");
+			hi[d] = 1;
+		}
+		const PlacedBox p = placeBox(lo, hi, 0, "recorder: only inner nodes can be observed");
+		for (int d = 0; d < D; d++) flat.push_back(pos[d] + (real)p.lo[d]);
+	}
+	auto rec = std::make_shared<Recorder>();
+	gcmxCheck(gcmx_recorder_create_points(ctx_, (int)points.size(), flat.data(), (int)quantities.size(), quantities.data(),
+	                                      capacity, &rec->handle),
+	          "gcmx_recorder_create_points");
+	rec->receivers = points.size();
+	rec->quantities = quantities.size();
+	return rec;
+}
+
+template <int D>
+void HipMesh<D>::record(Recorder& rec) const {
+	gcmxCheck(gcmx_record(ctx_, rec.handle), "gcmx_record");
+}
+
+template <int D>
+std::vector<real> HipMesh<D>::readRecorder(Recorder& rec) const {
+	const int count = rec.count();
+	std::vector<real> out((size_t)count * rec.quantities * rec.receivers);
+	if (count == 0) return out;
+	gcmxCheck(gcmx_recorder_read(rec.handle, 0, count, out.data()), "gcmx_recorder_read");
+	gcmxCheck(gcmx_recorder_reset(rec.handle), "gcmx_recorder_reset");
+	return out;
+}
+
+template <int D>
 std::array<uint64_t, 2> HipMesh<D>::transferBytes() const {
 	uint64_t v[2] = {0, 0};
 	gcmxCheck(gcmx_transfer_stats(ctx_, v), "gcmx_transfer_stats");
@@ -1258,6 +1314,20 @@ void Engine<D>::writeSnapshots(const int step) {
 		for (auto& snap : body.snapshotters) snap->snapshot(body.mesh.get(), step);
 }
 
+template <int D>
+void Engine<D>::flushSnapshots() const {
+	for (const Body& body : bodies)
+		for (auto& snap : body.snapshotters) snap->flush();
+}
+
+template <int D>
+Engine<D>::~Engine() {
+	try {
+		flushSnapshots();
+	} catch (...) {  // a destructor: what could not be written is lost
+	}
+}
+
 // ------------------------------------------------------------ save and resume --
 
 template <int D>
@@ -1300,6 +1370,7 @@ void forEachStateSlab(const std::array<int, D>& sizes, int M, size_t chunkBytes,
 
 template <int D>
 void Engine<D>::saveState(const std::string& path) const {
+	flushSnapshots();  // the files of the saved run are complete up to the saved step
 	const StateFileHeader h = stateHeader();
 	StateFileWriter w(path);
 	w.writeHeader(h);
@@ -1399,6 +1470,8 @@ SliceSnapshotter<D>::SliceSnapshotter(const Task& task) : Snapshotter(task) {
 	detectionArea = task.detector.area;
 	gridId = task.detector.gridId;
 	if (!detectionArea) throw Exception("SliceSnapshotter: detector area missing");
+	bufferSteps = task.detector.bufferSteps;
+	if (bufferSteps < 0) throw Exception("SliceSnapshotter: detector.bufferSteps is at least 0");
 }
 
 template <int D>
@@ -1418,7 +1491,9 @@ void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step
 			it[direction] = k;
 			nodes.push_back(it);
 		}
-		column = mesh->nodeList(nodes);
+		const int VzCode = quantityCode(PhysicalQuantities::T::Vx) + direction;
+		if (bufferSteps > 0) columnRec = mesh->recorder(nodes, {VzCode}, bufferSteps);
+		else column = mesh->nodeList(nodes);
 		if (mesh->id == gridId) {
 			// upper detector: the right border of the last axis inside the area (hpp:65-88)
 			if (!hasQuantityOf(mesh->model(), D, quantityToWrite)) throw Exception("quantity not present in the PDE vector");
@@ -1428,9 +1503,30 @@ void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step
 				if (detectionArea->contains(mesh->coords(j))) nodes.push_back(j);
 			});
 			if (nodes.empty()) throw Exception("SliceSnapshotter: no node in the detection area");
-			detector = mesh->nodeList(nodes);
+			if (bufferSteps > 0) detectorRec = mesh->recorder(nodes, {quantityCode(quantityToWrite)}, bufferSteps);
+			else detector = mesh->nodeList(nodes);
 		}
 	}
+	if (bufferSteps > 0) {
+		// the sample stays on the device: no wait here, the files at the next flush
+		mesh->record(*columnRec);
+		if (detectorRec) mesh->record(*detectorRec);
+		heldSteps.push_back(step);
+		heldTimes.push_back(Clock::Time());
+		if ((int)heldSteps.size() == bufferSteps) flush();
+		return;
+	}
+	const std::vector<real> Vz = mesh->gather(*column, {quantityCode(PhysicalQuantities::T::Vx) + direction});
+	std::vector<real> valuesInArea;
+	if (mesh->id == gridId) valuesInArea = mesh->gather(*detector, {quantityCode(quantityToWrite)});
+	writeFiles(mesh, step, Clock::Time(), Vz.data(), valuesInArea.data(), valuesInArea.size());
+}
+
+// The files of one snapshot from its column and, on body gridId, its detector values.
+template <int D>
+void SliceSnapshotter<D>::writeFiles(const HipMesh<D>* mesh, int step, real time, const real* Vz_,
+                                     const real* valuesInArea, size_t nValues) {
+	const int direction = D - 1;
 	std::array<int, D> it;
 	for (int i = 0; i < D; i++) it[i] = mesh->sizes[i] / 2;
 	std::vector<real> coordZ;
@@ -1438,18 +1534,91 @@ void SliceSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step
 		it[direction] = k;
 		coordZ.push_back(mesh->coords(it)[direction]);
 	}
-	const std::vector<real> Vz = mesh->gather(*column, {quantityCode(PhysicalQuantities::T::Vx) + direction});
+	const std::vector<real> Vz(Vz_, Vz_ + coordZ.size());
 	writeColumns(makeFileNameForSnapshot(std::to_string(mesh->id), step, "txt", "zaxis"),
 	             {coordZ, Vz});
 	if (mesh->id != gridId) return;
-	const std::vector<real> valuesInArea = mesh->gather(*detector, {quantityCode(quantityToWrite)});
 	real sum = 0;
-	for (real v : valuesInArea) sum += v;  // std::accumulate order
-	const real valueToWrite = sum / (real)valuesInArea.size();
-	times.push_back(Clock::Time());
+	for (size_t i = 0; i < nValues; i++) sum += valuesInArea[i];  // std::accumulate order
+	const real valueToWrite = sum / (real)nValues;
+	times.push_back(time);
 	seismo.push_back((precision)valueToWrite);
 	writeColumns(makeFileNameForSnapshot(std::to_string(mesh->id), step, "txt", "detector"),
 	             {times, seismo});
+}
+
+template <int D>
+void SliceSnapshotter<D>::flush() {
+	if (heldSteps.empty()) return;
+	const HipMesh<D>* mesh = listsOf;
+	const std::vector<real> Vz = mesh->readRecorder(*columnRec);
+	std::vector<real> inArea;
+	if (detectorRec) inArea = mesh->readRecorder(*detectorRec);
+	const std::vector<int> stepsHeld = std::move(heldSteps);
+	const std::vector<real> timesHeld = std::move(heldTimes);
+	heldSteps.clear();
+	heldTimes.clear();
+	const size_t nColumn = columnRec->receivers, nArea = detectorRec ? detectorRec->receivers : 0;
+	for (size_t s = 0; s < stepsHeld.size(); s++)
+		writeFiles(mesh, stepsHeld[s], timesHeld[s], Vz.data() + s * nColumn, inArea.data() + s * nArea, nArea);
+}
+
+template <int D>
+ReceiverSnapshotter<D>::ReceiverSnapshotter(const Task& task) : Snapshotter(task), settings(task.receivers) {
+	if (settings.points.empty()) throw Exception("ReceiverSnapshotter: no receivers (Task::Receivers::points)");
+	if (settings.quantities.empty() || settings.quantities.size() > GCMX_MAX_BORDER_Q)
+		throw Exception("ReceiverSnapshotter: 1 to 16 quantities");
+	if (settings.bufferSteps < 1) throw Exception("ReceiverSnapshotter: bufferSteps is at least 1");
+}
+
+template <int D>
+void ReceiverSnapshotter<D>::snapshotImpl(const AbstractGrid* mesh_, const int step) {
+	const HipMesh<D>* m = dynamic_cast<const HipMesh<D>*>(mesh_);
+	if (!m) throw Exception("ReceiverSnapshotter: not a cubic mesh");
+	if (m->id != settings.gridId) return;
+	if (mesh != m) {  // first use: the receivers go to the device once
+		std::vector<int> codes;
+		for (auto q : settings.quantities) {
+			if (!hasQuantityOf(m->model(), D, q)) throw Exception("quantity not present in the PDE vector");
+			codes.push_back(quantityCode(q));
+		}
+		std::array<int, D> first{};
+		const auto origin = m->coords(first);
+		std::vector<std::array<real, D>> positions;
+		for (const Real3& p : settings.points) {
+			std::array<real, D> pos;
+			for (int d = 0; d < D; d++) pos[d] = (p[d] - origin[d]) / m->h[d];
+			positions.push_back(pos);
+		}
+		rec = m->recorder(positions, codes, settings.bufferSteps);  // throws for a point outside the body
+		mesh = m;
+	}
+	m->record(*rec);
+	heldSteps.push_back(step);
+	heldTimes.push_back(Clock::Time());
+	if ((int)heldSteps.size() == settings.bufferSteps) flush();
+}
+
+template <int D>
+void ReceiverSnapshotter<D>::flush() {
+	if (heldSteps.empty()) return;
+	const std::vector<real> values = mesh->readRecorder(*rec);
+	const std::vector<real> timesHeld = std::move(heldTimes);
+	const int firstStep = heldSteps.front();
+	const size_t rows = heldSteps.size(), row = rec->quantities * rec->receivers;
+	heldSteps.clear();
+	heldTimes.clear();
+	const std::string fileName = makeFileNameForSnapshot(std::to_string(mesh->id), firstStep, "txt", "receivers");
+	std::FILE* f = std::fopen(fileName.c_str(), "w");
+	if (!f) throw Exception("cannot open " + fileName);
+	bool ok = true;
+	for (size_t s = 0; s < rows; s++) {
+		ok = ok && std::fprintf(f, "%.17g", timesHeld[s]) > 0;
+		for (size_t i = 0; i < row; i++) ok = ok && std::fprintf(f, "\t%.17g", values[s * row + i]) > 0;
+		ok = ok && std::fputc('\n', f) != EOF;
+	}
+	ok = std::fclose(f) == 0 && ok;
+	if (!ok) throw Exception("write failed: " + fileName);
 }
 
 template <int D>
@@ -1494,6 +1663,9 @@ template class VtkSnapshotter<3>;
 template class SliceSnapshotter<1>;
 template class SliceSnapshotter<2>;
 template class SliceSnapshotter<3>;
+template class ReceiverSnapshotter<1>;
+template class ReceiverSnapshotter<2>;
+template class ReceiverSnapshotter<3>;
 template class HipMaxwellViscosityOde<1>;
 template class HipMaxwellViscosityOde<2>;
 template class HipMaxwellViscosityOde<3>;

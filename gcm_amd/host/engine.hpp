@@ -76,6 +76,8 @@ protected:
 	virtual void nextTimeStep() = 0;
 	virtual real estimateTimeStep() = 0;
 	virtual void writeSnapshots(const int step) = 0;
+	/// Snapshotter::flush of every snapshotter (the end of run()).
+	virtual void flushSnapshots() const {}
 };
 
 /// grid/AbstractGrid.hpp -- what stage()/apply() receive and downcast.
@@ -273,6 +275,26 @@ public:
 	/// ceil(extent / stride) points per axis, counted from boxMin.
 	void snapshotArrays(const IntD& boxMin, const IntD& boxMax, const IntD& stride, const std::vector<int>& quantities,
 	                    float* velocity, float* values) const;
+	/// RECORDERS (gcmx_recorder): samples of the quantities at nodes, or at points
+	/// in this mesh's inner-index units, kept on the device (record: no host wait)
+	/// and read in batches.  Placed like nodeList: a stack member's receivers land
+	/// at its offset in the stack's context.
+	struct Recorder {
+		gcmx_recorder* handle = nullptr;
+		size_t receivers = 0, quantities = 0;
+		Recorder() = default;
+		Recorder(const Recorder&) = delete;
+		Recorder& operator=(const Recorder&) = delete;
+		~Recorder() { gcmx_recorder_destroy(handle); }
+		int count() const { return gcmx_recorder_count(handle); }
+	};
+	std::shared_ptr<Recorder> recorder(const std::vector<IntD>& nodes, const std::vector<int>& quantities,
+	                                   int capacity) const;
+	std::shared_ptr<Recorder> recorder(const std::vector<std::array<real, D>>& points,
+	                                   const std::vector<int>& quantities, int capacity) const;
+	void record(Recorder& rec) const;
+	/// Every sample held as [samples][quantities][receivers]; the recorder is empty afterwards.
+	std::vector<real> readRecorder(Recorder& rec) const;
 	/// Bytes the body's context copied {device -> host, host -> device} (gcmx_transfer_stats).
 	std::array<uint64_t, 2> transferBytes() const;
 	int numberOfMaterials() const { return (int)materialNumbers_.size(); }
@@ -474,6 +496,9 @@ template <int D>
 class SliceSnapshotter : public Snapshotter {
 public:
 	explicit SliceSnapshotter(const Task& task);
+	/// Task::Detector::bufferSteps > 0: the snapshots still on the device, written
+	/// as the files the unbuffered run writes.
+	void flush() override;
 
 protected:
 	void snapshotImpl(const AbstractGrid* mesh, const int step) override;
@@ -481,12 +506,46 @@ protected:
 private:
 	size_t gridId;
 	std::vector<real> times, seismo;
+	/// Buffered: the recorders of the two node lists and the step and time of
+	/// every sample they hold.
+	int bufferSteps = 0;
+	std::shared_ptr<typename HipMesh<D>::Recorder> columnRec, detectorRec;
+	std::vector<int> heldSteps;
+	std::vector<real> heldTimes;
+	void writeFiles(const HipMesh<D>* mesh, int step, real time, const real* Vz, const real* valuesInArea,
+	                size_t nValues);
 	std::shared_ptr<Area> detectionArea;
 	PhysicalQuantities::T quantityToWrite;
 	/// Made on first use, gathered at every snapshot: the column through sizes / 2
 	/// and the top-face nodes inside the detection area (forEachInner order).
 	const HipMesh<D>* listsOf = nullptr;
 	std::shared_ptr<typename HipMesh<D>::NodeList> column, detector;
+};
+
+/// Snapshotters::T::DETECTOR, which the reference declares (util/Enum.hpp:140) and
+/// never builds: seismograms at Task::Receivers' points of body gridId (other
+/// bodies: nothing).  A point p is position (p_d - coords(0)_d) / h_d in inner-index
+/// units; one outside the body's inner nodes throws at the first snapshot.  One
+/// sample per snapshot step goes to a device recorder; every bufferSteps samples
+/// and at flush() one text file snapshots[/outDir]/receivers/mesh<id>core00snap<step
+/// of its first row>.txt is written: per row the time, then the quantities x
+/// receivers values in quantity-major order, tab-separated, printed with %.17g.
+/// The files in step order are the whole record; none is reopened.
+template <int D>
+class ReceiverSnapshotter : public Snapshotter {
+public:
+	explicit ReceiverSnapshotter(const Task& task);
+	void flush() override;
+
+protected:
+	void snapshotImpl(const AbstractGrid* mesh, const int step) override;
+
+private:
+	const Task::Receivers settings;
+	const HipMesh<D>* mesh = nullptr;
+	std::shared_ptr<typename HipMesh<D>::Recorder> rec;
+	std::vector<int> heldSteps;
+	std::vector<real> heldTimes;
 };
 
 /// engine/cubic/AbstractFactory.hpp:22-54
@@ -540,6 +599,7 @@ public:
 		switch (type) {
 		case Snapshotters::T::VTK: return std::make_shared<VtkSnapshotter<D>>(task);
 		case Snapshotters::T::SLICESNAP: return std::make_shared<SliceSnapshotter<D>>(task);
+		case Snapshotters::T::DETECTOR: return std::make_shared<ReceiverSnapshotter<D>>(task);
 		default: throw Exception("Unknown or unsupported snapshotter");
 		}
 	}
@@ -554,6 +614,8 @@ class Engine : public AbstractEngine {
 public:
 	typedef CubicGrid<D> Grid;
 	explicit Engine(const Task& task, int device = 0);
+	/// Flushes the snapshotters (what they still hold on the device); never throws.
+	~Engine() override;
 	std::shared_ptr<const HipMesh<D>> getMesh(size_t gridId) const;
 	/// saveState streams every body's inner nodes in slabs along x of at most
 	/// Task::vtkSnapshotter.chunkBytes (one x plane at least) through readBox to a
@@ -567,6 +629,7 @@ protected:
 	void nextTimeStep() override;
 	real estimateTimeStep() override;
 	void writeSnapshots(const int step) override;
+	void flushSnapshots() const override;
 
 private:
 	struct Body {

@@ -33,6 +33,10 @@ public:
 	void snapshot(const AbstractGrid* grid, const int step) {
 		if (step % stepsPerSnap == 0) snapshotImpl(grid, step);
 	}
+	/// Host only: write what a snapshotter still holds back (samples kept on the
+	/// device).  The engine calls it at the end of run(), before saveState and from
+	/// its destructor.
+	virtual void flush() {}
 
 protected:
 	virtual void snapshotImpl(const AbstractGrid* grid, const int step) = 0;

@@ -339,7 +339,23 @@ struct Task {
 		std::vector<PhysicalQuantities::T> quantities;
 		std::shared_ptr<Area> area;
 		size_t gridId = 0;
+		/// Host only: the cubic SliceSnapshotter keeps this many snapshots on the
+		/// device (two gcmx recorders, the column and the detector face) and writes
+		/// their files when they are held and at a flush -- the same files, byte for
+		/// byte.  0: every snapshot waits for the device and writes at once.
+		int bufferSteps = 0;
 	} detector;
+
+	/// Host only: receivers of the DETECTOR snapshotter (cubic::ReceiverSnapshotter),
+	/// points in physical coordinates inside body gridId, blended from the nodes
+	/// around them (gcmx_recorder_create_points).  One sample per snapshot step;
+	/// bufferSteps samples are kept on the device between two files.
+	struct Receivers {
+		size_t gridId = 0;
+		std::vector<Real3> points;
+		std::vector<PhysicalQuantities::T> quantities;
+		int bufferSteps = 256;
+	} receivers;
 };
 
 }  // namespace gcm

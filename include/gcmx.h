@@ -295,6 +295,51 @@ void        gcmx_node_list_destroy(gcmx_node_list* list);
 /* out[q][i] = quantity q at node i of the list; n_q in 1..GCMX_MAX_BORDER_Q. */
 gcmx_status gcmx_gather(gcmx_ctx* ctx, const gcmx_node_list* list, int n_q, const int* quantities,
                         double* out);
+/* A recorder: receivers of a context and a device buffer of `capacity` samples of
+ * n_q quantities at each of them (capacity * n_q * n doubles; sample s starts at
+ * element s * n_q * n, laid out [q][i]).  What gcmx_gather gives once and
+ * synchronously a recorder collects on the context's stream and hands over in
+ * batches: a seismogram costs one host wait per batch, not one per step.
+ * Quantities are gcmx_gather's, n_q in 1..GCMX_MAX_BORDER_Q, capacity >= 1; a
+ * buffer that cannot be allocated is GCMX_ERR_OOM and leaves nothing behind.
+ * gcmx_recorder_create takes the receivers of a node list and copies them: the
+ * list may be destroyed afterwards.
+ * gcmx_recorder_create_points takes n_points positions [n][dim] in inner-index
+ * units (position i_d is inner node i_d).  Every axis d < dim needs sizes_d >= 2
+ * and a finite 0 <= pos_d <= sizes_d - 1, else GCMX_ERR_INVALID_ARG.  The value
+ * is the multilinear blend of the 2^dim nodes around the point: base index
+ * i_d = min((int)floor(pos_d), sizes_d - 2), t_d = pos_d - (double)i_d; corner k
+ * in [0, 2^dim) takes bit (k >> (dim-1-d)) & 1 on axis d (the last axis runs
+ * fastest) and the weight f_0, then * f_1, then * f_2 with f_d = bit ? t_d :
+ * (1.0 - t_d); the sample is acc = w_0 v_0, then acc = acc + w_k v_k for
+ * ascending k, v_k the quantity at corner k as gcmx_gather evaluates it (the
+ * elastic PRESSURE per corner, then blended), every product and every sum
+ * rounded on its own.  A node recorder's sample is gcmx_gather's bit for bit.
+ * gcmx_record enqueues the sample of the CURRENT layer into slot count on the
+ * context's stream and adds one to count: it waits for nothing (not for the
+ * stream, not for a pending halo exchange -- receivers are inner nodes, which an
+ * exchange never writes), copies nothing and leaves gcmx_transfer_stats as it
+ * was.  Valid after any step call and between gcmx_stage calls.  A full recorder
+ * (count == capacity) is GCMX_ERR_STATE: nothing is enqueued or changed.  A
+ * recorder of another context, or one whose context is destroyed, is
+ * GCMX_ERR_INVALID_ARG.
+ * gcmx_recorder_read waits for the stream and copies samples first ... first +
+ * count - 1 as out[count][n_q][n] in one copy of exactly count * n_q * n * 8
+ * bytes (counted by gcmx_transfer_stats); 0 <= first, count >= 1, first + count
+ * <= the samples held, else GCMX_ERR_INVALID_ARG.  gcmx_recorder_reset sets count
+ * to 0 on the host; the device is not touched.
+ * gcmx_destroy detaches the context's recorders after its own waits: their
+ * samples stay readable, gcmx_recorder_destroy frees them at any time. */
+typedef struct gcmx_recorder gcmx_recorder;
+gcmx_status gcmx_recorder_create(gcmx_ctx* ctx, const gcmx_node_list* list, int n_q, const int* quantities,
+                                 int capacity, gcmx_recorder** out);
+gcmx_status gcmx_recorder_create_points(gcmx_ctx* ctx, int n_points, const double* positions, int n_q,
+                                        const int* quantities, int capacity, gcmx_recorder** out);
+void        gcmx_recorder_destroy(gcmx_recorder* recorder);
+gcmx_status gcmx_record(gcmx_ctx* ctx, gcmx_recorder* recorder);
+int         gcmx_recorder_count(const gcmx_recorder* recorder);
+gcmx_status gcmx_recorder_read(gcmx_recorder* recorder, int first, int count, double* out);
+gcmx_status gcmx_recorder_reset(gcmx_recorder* recorder);
 /* The Float32 arrays of the inner box [box_min, box_max) (entries >= dim are
  * ignored) in VTK point order, n = the box's nodes with x fastest, then y, then z
  * (VtkIterator, CubicGrid.hpp:34): velocity[n][3] when want_velocity (components
