@@ -10,7 +10,20 @@ scales the stored stresses), and the kernel the profile must name, so that a
 case cannot drift onto another instance unnoticed.
 
 Both sides return, per step, the list of states to compare: one for a one-pass
-step, one per stage for the per-stage paths.  Each is a grid [X(, Y(, Z)), M]."""
+step, one per stage for the per-stage paths.  Each is a grid [X(, Y(, Z)), M].
+
+Names with the prefix "gp-" are the general-position twins of the homogeneous
+isotropic entries: the same shape, marks and instance, on the material ISO_GP,
+none of whose structural coefficients is a power of two or equals another (on
+(4, 2, 1) every one is, and four of them equal the kernels' constants 0.5 and
+1), at the time step courant_tau gives.  Their grid steps are H_GP, unequal, so
+that each axis has Newton coefficients, Lagrange weights and floor(q) of its
+own, wherever the instance admits that.  A UNI, HET or ZS instance of
+k_step_tx2 does not: the dispatch takes one only when the three axes' tables
+are bitwise equal (same_axis, kernels_xyz.hip), and the kernel then reads the
+X axis' table for all three stages.  The twins of those entries take the equal
+steps H_GP_EQ, which keeps them on their instance; tests/test_states_cpu.py
+states which twin has which steps and what either medium separates."""
 import copy
 
 import numpy as np
@@ -22,23 +35,41 @@ from tests.test_gpu_2d import FACE2_CASES, face_body2, faces_at2
 from tests.test_gpu_faces import conditions_at, face_body, face_maps, faces_at, free, partial_body
 from tests.test_gpu_ortho import H_A, ortho_body
 from tests.test_gpu_ortho_het import het_body
+from tests.test_gpu_plane_builds import ISO as ISO_GP
 from tests.test_gpu_wide_access import MATS, TAU_HET
 
 FREE_ALL = [(0, 0, free(0)), (1, 0, free(1)), (2, 0, free(2))]
 FREE_YZ = [(1, 0, free(1)), (2, 0, free(2))]
 H_ACOUSTIC = (0.5, 0.4, 0.3)
 TAU0, TAU0_HET = (3.0,), (3.0, 0.7)  # Maxwell relaxation times, per material
+ISO_DYADIC = (4.0, 2.0, 1.0)
+# The general-position medium (see the header): ISO_GP on unequal steps.  At
+# Courant 0.9 q = |L| tau / h is 0.643 / 0.288, 0.9 / 0.403, 0.409 / 0.183
+# (P / S per axis); at Courant 1.5 floor(q) of the P waves is (1, 1, 0).
+H_GP = (0.7, 0.5, 1.1)
+H_GP_EQ = (H_GP[0],) * 3  # for the instances that take equal axes only
+# 2-D: at Courant 1.5 floor(q) of the P waves is (1, 0); with a second step of
+# 0.5 both floors are 1, and a mix-up of the axes' floors would not show
+H_GP2 = (0.7, 1.1)
 
 
 def courant_tau(b, courant=0.9):
     return courant * min(b.h[:b.D]) / b.maximal_eigenvalue
 
 
+def courant15_tau(b):
+    return courant_tau(b, 1.5)
+
+
 # ------------------------------------------------------------ material sets --
 # name -> body(bs, sizes) with that set's tables, and its Courant 0.9 time step
 
-def _iso(bs, sizes, start=None):
-    return oracle_body(3, bs, sizes, start=start)
+def _iso(bs, sizes, start=None, h=None, material=ISO_DYADIC):
+    return oracle_body(3, bs, sizes, start=start, h=h, materials=(material,))
+
+
+def _gp(bs, sizes, start=None, h=H_GP):
+    return _iso(bs, sizes, start, h=h, material=ISO_GP)
 
 
 def _iso_het(bs, sizes):
@@ -47,8 +78,12 @@ def _iso_het(bs, sizes):
     return b
 
 
-def _iso2d(bs, sizes):
-    return oracle_body(2, bs, sizes, h=[1.0, 0.5])
+def _iso2d(bs, sizes, h=(1.0, 0.5), material=ISO_DYADIC):
+    return oracle_body(2, bs, sizes, h=list(h), materials=(material,))
+
+
+def _gp2d(bs, sizes):
+    return _iso2d(bs, sizes, h=H_GP2, material=ISO_GP)
 
 
 def _table2d(bs, sizes):
@@ -87,7 +122,21 @@ MATERIAL_SETS = {
     "iso2d": (_iso2d, lambda b: 0.45),
     "table2d": (_table2d, lambda b: 0.45),
     "acoustic": (_acoustic, courant_tau),
+    "iso_gp": (_gp, courant_tau),
+    "iso_gp_eq": (lambda bs, sizes: _gp(bs, sizes, h=H_GP_EQ), courant_tau),
+    "iso2d_gp": (_gp2d, courant_tau),
 }
+
+
+def scaled_areas(conds, h):
+    """The conditions of a face-map entry (MAP_64, MAP_1024: boxes in physical
+    coordinates on unit steps) on steps `h`: every box bound times its axis' step."""
+    out = []
+    for axis, side, area, vals in conds:
+        assert area[0] == "box"
+        lo, hi = (tuple(v * s for v, s in zip(bound, h)) for bound in area[1:])
+        out.append((axis, side, ("box", lo, hi), vals))
+    return out
 
 
 # ------------------------------------------------------------------ entries --
@@ -257,13 +306,16 @@ class Run:
             c.close()
 
 
-def _tx2(name, bs, sizes, path, start=None, **kw):
+def _tx2(name, bs, sizes, path, start=None, gp=None, **kw):
     """path: "wide" (16-byte accesses), "n8" (a UNI launch on the 8-byte path) or
-    "!uni" (idle lanes: the 8-byte instances)."""
+    "!uni" (idle lanes: the 8-byte instances).  gp: the steps of a general-position
+    twin (ISO_GP at Courant 0.9)."""
     marks = {"wide": (", UNI",), "n8": (", UNI", ", N8"), "!uni": ("!UNI",)}[path]
     absent = {"wide": (", N8",), "n8": (), "!uni": ()}[path]
-    return Launch(name, "step", lambda: _iso(bs, sizes, start), 0.9, f"k_step_tx2<{bs}, ", marks + kw.pop("marks", ()),
-                  absent, fma_tag=True, **kw)
+    make, tau = (lambda: _iso(bs, sizes, start), 0.9) if gp is None else \
+        (lambda: _gp(bs, sizes, start, h=gp), courant_tau)
+    return Launch(name, "step", make, tau, f"k_step_tx2<{bs}, ", marks + kw.pop("marks", ()), absent, fma_tag=True,
+                  **kw)
 
 
 def _het(name, bs, sizes, path):
@@ -272,10 +324,10 @@ def _het(name, bs, sizes, path):
                   (", N8",) if path == "wide" else (), fma_tag=True)
 
 
-def _stages(name, sizes, path_name):
+def _stages(name, sizes, path_name, make=_iso, tau=0.9):
     path = {"split": PATH_SPLIT, "generic": PATH_GENERIC}[path_name]
     prefix = {"split": ("k_march<", "k_line_z"), "generic": ("k_stage_generic",)}[path_name]
-    return Launch(name, "stages", lambda: _iso(2, sizes), 0.9, prefix, path=path, expect_path=path_name)
+    return Launch(name, "stages", lambda: make(2, sizes), tau, prefix, path=path, expect_path=path_name)
 
 
 def _ortho(name, bs, sizes, h=H_A, tau=courant_tau, marks=(", KF0",)):
@@ -286,11 +338,19 @@ def _ortho(name, bs, sizes, h=H_A, tau=courant_tau, marks=(", KF0",)):
 # Face entries take free surfaces (every prescribed value 0): the step stays
 # linear and homogeneous, which the impulse footprints and the power-of-two
 # scaling of tests/test_gpu_states.py rest on.
-def _face2d():
+def _face2d(gp=False):
     bs, sizes, conds, courant, path = FACE2_CASES["free_all"]
     assert path == "fused"
+    if gp:
+        make = lambda: face_body2(bs, sizes, conds, h=H_GP2, material=ISO_GP)
+        return Launch("gp-2d-faces-free4-30x70", "faces", make, courant_tau, "k_step2d_iso<2, ", (", FACES",),
+                      conds=conds, faces_at=faces_at2)
     return Launch("2d-faces-free4-30x70", "faces", lambda: face_body2(bs, sizes, conds), courant, "k_step2d_iso<2, ",
                   (", FACES",), conds=conds, faces_at=faces_at2)
+
+
+def _gp_faces(bs, sizes, conds=FREE_ALL, h=H_GP):
+    return lambda: face_body(3, bs, sizes, conds, h=h, material=ISO_GP)
 
 
 def _faces3(name, bs, sizes, marks, conds=FREE_ALL, tau=0.9, make_body=None, prefix=None, absent=("!FACES",)):
@@ -307,10 +367,12 @@ def _ode(name, bs, make_body, tau0, marks, tau=0.9, conds=None, absent=()):
                   fma_tag=True, tau0=tau0, conds=conds, faces_at=lambda c, t: faces_at(3, c, t))
 
 
-def _map(name, bs, sizes, conds, marks):
-    """gcmx_step_face_map; conds: (axis, side or 0, area, values) of partial_body."""
-    return Launch(name, "map", lambda: partial_body(bs, sizes, conds), 0.9, f"k_step_tx2<{bs}, ", marks, ("!FACES",),
-                  fma_tag=True)
+def _map(name, bs, sizes, conds, marks, gp=None):
+    """gcmx_step_face_map; conds: (axis, side or 0, area, values) of partial_body.
+    gp: the steps of a general-position twin, whose areas are `conds` scaled."""
+    make, tau = (lambda: partial_body(bs, sizes, conds), 0.9) if gp is None else \
+        (lambda: partial_body(bs, sizes, scaled_areas(conds, gp), materials=(ISO_GP,), h=gp), courant_tau)
+    return Launch(name, "map", make, tau, f"k_step_tx2<{bs}, ", marks, ("!FACES",), fma_tag=True)
 
 
 def _acoustic_launch(name, bs, sizes, zt, h=H_ACOUSTIC, tau=courant_tau, kf0="KF0"):
@@ -395,5 +457,60 @@ CATALOG = [
     Launch("2d-table-bs2-30x300", "step", lambda: _table2d(2, [30, 300]), 0.45, "k_step2d<2, "),
     _face2d(),
 ]
+
+# The general-position twins (see the header).  EQ: the entry's instance takes
+# bitwise-equal axes only (UNI, ZS), so its twin has equal steps.
+EQ = H_GP_EQ
+CATALOG += [
+    # ---- k_step_tx2
+    _tx2("gp-tx2-wide-bs2-4x5x64", 2, [4, 5, 64], "wide", gp=EQ),
+    _tx2("gp-tx2-wide-bs2-3x6x128", 2, [3, 6, 128], "wide", gp=EQ),
+    _tx2("gp-tx2-wide-bs1-4x5x64", 1, [4, 5, 64], "wide", gp=EQ),
+    _tx2("gp-tx2-wide-start1-bs2-4x5x64", 2, [4, 5, 64], "wide", start=[1, 0, 0], gp=EQ),
+    _tx2("gp-tx2-n8-bs2-3x6x256", 2, [3, 6, 256], "n8", gp=EQ),
+    _tx2("gp-tx2-!uni-bs2-4x6x40", 2, [4, 6, 40], "!uni", gp=H_GP),
+    _tx2("gp-tx2-zs-bs2-4x12x1024", 2, [4, 12, 1024], "wide", marks=(", ZS",), gp=EQ),
+    # ---- floor(q) of the P waves (1, 1, 0), of the S waves 0
+    Launch("gp-courant15-bs2-4x6x64", "step", lambda: _gp(2, [4, 6, 64]), courant15_tau,
+           ("k_step_tx2<2, ", "k_fused_xyz<2, "), ("!KF0",), fma_tag=True),
+    _faces3("gp-tx2-faces-courant15-bs2-4x8x64", 2, [4, 8, 64], ("!KF0", ", FACES"), conds=FREE_YZ, tau=courant15_tau,
+            make_body=_gp_faces(2, [4, 8, 64], FREE_YZ)),
+    # ---- faces
+    _faces3("gp-tx2-faces-free6-bs2-4x8x64", 2, [4, 8, 64], (", UNI", ", FACES"), tau=courant_tau,
+            make_body=_gp_faces(2, [4, 8, 64], h=EQ), absent=("!FACES", ", N8")),
+    _faces3("gp-tx2-zs-faces-free6-bs2-4x12x1024", 2, [4, 12, 1024], (", UNI", ", FACES", ", ZS"), tau=courant_tau,
+            make_body=_gp_faces(2, [4, 12, 1024], h=EQ), prefix="k_step_tx2<2, 512, KF0, "),
+    _faces3("gp-tx2-zs-faces-free6-bs1-4x8x1024", 1, [4, 8, 1024], (", UNI", ", FACES", ", ZS"), tau=courant_tau,
+            make_body=_gp_faces(1, [4, 8, 1024], h=EQ), prefix="k_step_tx2<1, 512, KF0, "),
+    _faces3("gp-tx2-faces-!uni-free6-bs2-4x8x40", 2, [4, 8, 40], ("!UNI", ", FACES"), tau=courant_tau,
+            make_body=_gp_faces(2, [4, 8, 40])),
+    # unequal axes: the !UNI instance on whole waves (the original runs a UNI one)
+    _faces3("gp-tx2-faces-free6-bs1-4x6x64", 1, [4, 6, 64], (", FACES",), tau=courant_tau,
+            make_body=_gp_faces(1, [4, 6, 64])),
+    # ---- maps, their areas scaled to the steps
+    _map("gp-tx2-map-bs2-6x12x64", 2, [6, 12, 64], MAP_64, (", FACES",), gp=H_GP),
+    _map("gp-tx2-map-zs-bs2-4x10x1024", 2, [4, 10, 1024], MAP_1024, (", FACES", ", ZS"), gp=EQ),
+    # ---- the folded ODE
+    _ode("gp-tx2-ode-bs2-4x6x64", 2, lambda: _gp(2, [4, 6, 64]), TAU0, ("<2, 64, ",), tau=courant_tau),
+    _ode("gp-tx2-faces-ode-bs2-4x8x64", 2, _gp_faces(2, [4, 8, 64], h=EQ), TAU0, (", UNI", ", FACES"), tau=courant_tau,
+         conds=FREE_ALL, absent=("!FACES", ", N8")),
+    _ode("gp-tx2-zs-ode-bs2-4x12x1024", 2, lambda: _gp(2, [4, 12, 1024], h=EQ), TAU0, (", UNI", ", ZS"),
+         tau=courant_tau),
+    # ---- other 3-D paths; the second slab starts on an odd global plane
+    Launch("gp-fused_xyz-bs3-4x7x100", "step", lambda: _gp(3, [4, 7, 100]), courant_tau, "k_fused_xyz<3, ",
+           fma_tag=True),
+    _stages("gp-split-bs2-9x4x300", [9, 4, 300], "split", make=_gp, tau=courant_tau),
+    Launch("gp-slabs-bfirst-bs2-7+9x6x64", "slabs", lambda: _gp(2, [16, 6, 64]), courant_tau, "k_step_tx2<2, ",
+           fma_tag=True, slabs=(7, 9)),
+    # ---- 2-D; mixed: floor(q) of the P waves (1, 0)
+    Launch("gp-2d-iso-bs2-21x70", "step", lambda: _gp2d(2, [21, 70]), courant_tau, "k_step2d_iso<2, "),
+    Launch("gp-2d-iso-bs1-130x253", "step", lambda: _gp2d(1, [130, 253]), courant_tau, "k_step2d_iso<1, "),
+    _face2d(gp=True),
+    Launch("gp-2d-iso-mixed-bs2-21x70", "step", lambda: _gp2d(2, [21, 70]), courant15_tau, "k_step2d_iso<2, ",
+           ("!KF0",)),
+]
 BY_NAME = {e.name: e for e in CATALOG}
+# twin -> original (the slab twin splits 7 + 9 where the original splits 8 + 8,
+# and the mixed-floor 2-D entry has no original)
+TWINS = {n: n[len("gp-"):] for n in BY_NAME if n.startswith("gp-") and n[len("gp-"):] in BY_NAME}
 assert len(BY_NAME) == len(CATALOG)

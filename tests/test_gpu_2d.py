@@ -167,8 +167,8 @@ def free2(axis, normal=lambda t: 0.0):
     return {q[0]: normal, q[1]: lambda t: 0.0}
 
 
-def face_body2(bs, sizes, conditions):
-    """conditions: (axis, side or 0 for both faces, {quantity: f(t)}), h = 1."""
+def face_body2(bs, sizes, conditions, h=(1.0, 1.0), material=(4.0, 2.0, 1.0)):
+    """conditions: (axis, side or 0 for both faces, {quantity: f(t)}); steps `h`."""
     from oracle import oracle as O
     bcs = []
     for axis, side, vals in conditions:
@@ -176,12 +176,12 @@ def face_body2(bs, sizes, conditions):
             area = ("infinite",)
         else:
             lo, hi = [-1e3] * 3, [1e3] * 3
-            c = 0.0 if side < 0 else float(sizes[axis] - 1)
-            lo[axis], hi[axis] = c - 0.5, c + 0.5
+            c = 0.0 if side < 0 else float(sizes[axis] - 1) * h[axis]
+            lo[axis], hi[axis] = c - 0.5 * h[axis], c + 0.5 * h[axis]
             area = ("box", tuple(lo), tuple(hi))
         bcs.append(O.BorderCondition(axis, area, vals))
-    t = O.Task(D=2, border_size=bs, h=[1.0, 1.0], cubics={0: (list(sizes), [0, 0])}, courant=0.9,
-               default_material=O.Material(4.0, 2.0, 1.0), number_of_snaps=1, border_conditions={0: bcs})
+    t = O.Task(D=2, border_size=bs, h=list(h), cubics={0: (list(sizes), [0, 0])}, courant=0.9,
+               default_material=O.Material(*material), number_of_snaps=1, border_conditions={0: bcs})
     return O.Engine(t).bodies[0]
 
 

@@ -242,6 +242,28 @@ def test_engine_maxwell_ode(H, D, tau0_b, path):
     assert he.ode_fused(0) == (path == "fused")
 
 
+def test_engine_on_the_general_medium(H):
+    """Task -> Engine::run on the general-position medium of tests/launch_catalog.py
+    (ISO_GP on the unequal steps H_GP): the host's own ElasticModel matrices and
+    estimateTimeStep, free surfaces on every face and the Maxwell ODE, one pass per
+    step with the ODE in its stores; inner nodes bitwise == the oracle engine.  Every
+    other engine run of this suite with a one-pass step has (4, 2, 1) on unit steps,
+    where the axes' tables coincide and the matrix entries are powers of two."""
+    from tests.launch_catalog import H_GP, ISO_GP
+    from tests.test_gpu_faces import FREE
+    zero = lambda t: 0.0
+    s = spec(3, 2, H_GP, {0: ([6, 8, 64], [0, 0, 0])}, 0.9, ISO_GP + (3.0,), snaps=3,
+             quantities=[(("sphere", 2.5, (1.4, 2.0, 33.0)), "PRESSURE", 2.0)],
+             vectors=[(("box", (0.5, 0.7, 20.0), (3.0, 2.8, 50.0)), [0.1 * (i + 1) for i in range(9)])],
+             borders={0: [(d, ("infinite",), {q: zero for q in FREE[d]}) for d in range(3)]},
+             odes={0: ["MAXWELL_VISCOSITY"]})
+    oe, he = run_both(H, s)
+    assert he.steps == 3
+    assert he.last_path(0) == "fused" and he.ode_fused(0)
+    assert np.any(inner(he.pde(0), 2, 3) != 0)
+    assert_bodies_equal(oe, he, s, inner_only=True)
+
+
 @pytest.mark.parametrize("faces", [False, True])
 def test_step_ode_fused_equals_step_then_ode(G, faces):
     """gcmx_step_ode == gcmx_step / gcmx_step_faces followed by gcmx_ode_maxwell,

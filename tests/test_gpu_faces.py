@@ -30,24 +30,27 @@ def G():
     return gcm_amd
 
 
-def face_area(D, sizes, axis, side):
-    """An axis-aligned box holding exactly the nodes of one face (h = 1, start 0;
-    the other axes unbounded for any grid here, rows of 1024 included)."""
+def face_area(D, sizes, axis, side, h=None):
+    """An axis-aligned box holding exactly the nodes of one face (start 0, steps
+    `h`, 1 unless given: the face lies at (size - 1) * h, the box reaches half a
+    step either way; the other axes unbounded for any grid here, rows of 1024
+    included)."""
     lo = [-1e6] * 3
     hi = [1e6] * 3
-    c = 0.0 if side < 0 else float(sizes[axis] - 1)
-    lo[axis], hi[axis] = c - 0.5, c + 0.5
+    step = 1.0 if h is None else float(h[axis])
+    c = 0.0 if side < 0 else float(sizes[axis] - 1) * step
+    lo[axis], hi[axis] = c - 0.5 * step, c + 0.5 * step
     return ("box", tuple(lo), tuple(hi))
 
 
-def face_body(D, bs, sizes, conditions):
+def face_body(D, bs, sizes, conditions, h=None, material=(4.0, 2.0, 1.0)):
     """conditions: list of (axis, side or 0 for both faces, {quantity: f(t)})."""
     bcs = []
     for axis, side, vals in conditions:
-        area = ("infinite",) if side == 0 else face_area(D, sizes, axis, side)
+        area = ("infinite",) if side == 0 else face_area(D, sizes, axis, side, h)
         bcs.append(O.BorderCondition(axis, area, vals))
-    t = O.Task(D=D, border_size=bs, h=[1.0] * D, cubics={0: (list(sizes), [0] * D)}, courant=0.9,
-               default_material=O.Material(4.0, 2.0, 1.0), number_of_snaps=1,
+    t = O.Task(D=D, border_size=bs, h=[1.0] * D if h is None else list(h), cubics={0: (list(sizes), [0] * D)},
+               courant=0.9, default_material=O.Material(*material), number_of_snaps=1,
                border_conditions={0: bcs})
     return O.Engine(t).bodies[0]
 
@@ -372,11 +375,13 @@ PARTIAL_CASES = {
 }
 
 
-def partial_body(bs, sizes, conds, materials=((4.0, 2.0, 1.0),)):
+def partial_body(bs, sizes, conds, materials=((4.0, 2.0, 1.0),), h=None):
+    """`conds`' areas are in physical coordinates: on steps `h` other than 1 the
+    caller scales them (tests/launch_catalog.py: scaled_areas)."""
     bcs = []
     for axis, side, area, vals in conds:
         if side != 0:  # restrict the area to one face: intersect with the face slab
-            fa = face_area(3, sizes, axis, side)
+            fa = face_area(3, sizes, axis, side, h)
             lo = [max(a, b) for a, b in zip(fa[1], area[1])] if area[0] == "box" else None
             if area[0] == "box":
                 hi = [min(a, b) for a, b in zip(fa[2], area[2])]
@@ -385,8 +390,8 @@ def partial_body(bs, sizes, conds, materials=((4.0, 2.0, 1.0),)):
                 pass
         bcs.append(O.BorderCondition(axis, area, vals))
     mats = [O.Material(*m) for m in materials]
-    t = O.Task(D=3, border_size=bs, h=[1.0] * 3, cubics={0: (list(sizes), [0] * 3)}, courant=0.9,
-               default_material=mats[0], inhomogeneities=[(("infinite",), m) for m in mats[1:]],
+    t = O.Task(D=3, border_size=bs, h=[1.0] * 3 if h is None else list(h), cubics={0: (list(sizes), [0] * 3)},
+               courant=0.9, default_material=mats[0], inhomogeneities=[(("infinite",), m) for m in mats[1:]],
                number_of_snaps=1, border_conditions={0: bcs})
     return O.Engine(t).bodies[0]
 

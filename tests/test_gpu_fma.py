@@ -175,15 +175,19 @@ def test_fma_slab_group_equals_whole_bitwise(G, sched, xs):
     x index), so a slab starting at an odd plane begins with a half pair and
     every node keeps its pair position (TestEngine.cpp:27-87 / TestMPI.cpp:146-150:
     split == unsplit, bitwise)."""
+    slab_group_equals_whole(G, sched, xs)
+
+
+def slab_group_equals_whole(G, sched, xs, material=(4, 2, 1), h=(1.0, 1.0, 1.0), tau=0.9, path=None):
     import gcm_amd
     from gcm_amd.host import isotropic_elastic_matrices
     Y, Z, seed = 20, 64, 0x5EED
     Xg = sum(xs)
-    U, U1, L = isotropic_elastic_matrices(3, 4, 2, 1)
+    U, U1, L = isotropic_elastic_matrices(3, *material)
     sc = {"xslab": G.SCHED_XSLAB, "bfirst": G.SCHED_BFIRST, "single": G.SCHED_SINGLE}[sched]
     slabs, x0 = [], 0
     for X in xs:
-        c = gcm_amd.Context(3, 2, [X, Y, Z], start=[x0, 0, 0])
+        c = gcm_amd.Context(3, 2, [X, Y, Z], start=[x0, 0, 0], h=list(h))
         c.set_materials(U[None], U1[None], L[None])
         c.fp_mode = G.FP_FMA
         c.fill_random([Xg, Y, Z], seed)
@@ -191,26 +195,39 @@ def test_fma_slab_group_equals_whole_bitwise(G, sched, xs):
         slabs.append(c)
         x0 += X
     G.comm_init_local(slabs)
-    w = gcm_amd.Context(3, 2, [Xg, Y, Z])
+    w = gcm_amd.Context(3, 2, [Xg, Y, Z], h=list(h))
     w.set_materials(U[None], U1[None], L[None])
     w.fp_mode = G.FP_FMA
     w.fill_random([Xg, Y, Z], seed)
     steps = 3
-    G.local_group_steps(slabs, 0.9, steps)
+    G.local_group_steps(slabs, tau, steps)
     for _ in range(steps):
-        w.step(0.9)
+        w.step(tau)
+    assert path is None or all(c.last_path == path for c in slabs + [w])
     inner = lambda c: c.download().reshape(tuple(s + 4 for s in c.sizes) + (9,))[2:-2, 2:-2, 2:-2]
     got = np.concatenate([inner(c) for c in slabs], axis=0)
     assert np.array_equal(got, inner(w)), rel_l2(got, inner(w))
-    b = oracle_body(3, 2, [Xg, Y, Z])
+    b = oracle_body(3, 2, [Xg, Y, Z], h=list(h), materials=(tuple(float(v) for v in material),))
     O.fill_random(b, [Xg, Y, Z], seed)
     for _ in range(steps):
         for s in range(3):
-            b.stage(s, 0.9)
+            b.stage(s, tau)
     r = rel_l2(got, b.inner_view())
     assert r <= TOL, r
     for c in slabs + [w]:
         c.close()
+    return r
+
+
+def test_fma_slab_group_equals_whole_on_the_general_medium(G):
+    """The claim above -- every node runs the same contracted sequence in any slab
+    -- on ISO_GP and the unequal steps H_GP (tests/launch_catalog.py), where the
+    transform's products round and its contracted row sums differ from the exact
+    ones; on (4, 2, 1) they do not, and only the Lagrange feet are tested."""
+    from tests.launch_catalog import H_GP, ISO_GP, _gp, courant_tau
+    tau = courant_tau(_gp(2, [4, 4, 4]))
+    r = slab_group_equals_whole(G, "bfirst", [7, 5, 9, 3], material=ISO_GP, h=H_GP, tau=tau, path="fused")
+    print(f"FMA slab group on the general medium: relative L2 to the oracle {r:.3e}")
 
 
 @pytest.mark.slow

@@ -459,6 +459,55 @@ def test_heterogeneous_one_pass_step_matches_oracle(G, bs, sizes, layout):
     ctx.close()
 
 
+@pytest.mark.parametrize("steps,path", [("unit", "fused"), ("h_gp", "generic")])
+def test_heterogeneous_unequal_steps_take_the_stages(G, steps, path):
+    """The heterogeneous one-pass step keeps one table per material for all three
+    stages, which is right only where the three axes' tables are bitwise equal
+    (Medium::IsoHet, build_tables).  On the unequal steps H_GP they are not (each
+    axis has its own q), so the step must turn onto the per-stage kernels, which
+    read per-axis tables; on unit steps the same materials and ids stay on the
+    one-pass step.  Either way 3 steps == the oracle's stages, bitwise."""
+    from tests.launch_catalog import H_GP, MATS, courant_tau
+    b = oracle_body(3, 2, [5, 7, 64], h=H_GP if steps == "h_gp" else None, materials=MATS, courant=0.9)
+    random_materials(b, seed=5)
+    random_state(b, seed=6, ghosts=False)
+    tau = courant_tau(b)  # Courant 0.9 on the fastest material and the smallest step: floor(q) = 0
+    ctx = context_for(b)
+    for step in range(3):
+        for s in range(3):
+            b.stage(s, tau)
+        ctx.step(tau)
+        assert ctx.last_path == path, f"ran {ctx.last_path}"
+        assert_same(ctx, b, f"HET on {steps} steps, step {step}")
+    ctx.close()
+
+
+@pytest.mark.parametrize("sizes,kernel", [([4, 5, 64], "k_step_tx2<2, 64, KF0, !UNI, "),
+                                          ([3, 6, 256], "k_step_tx2<2, 256, KF0, !UNI, "),
+                                          ([4, 12, 1024], "k_fused_xyz<2, 1024, KF0, !UNI")])
+def test_unequal_steps_leave_the_one_table_instances(G, sizes, kernel):
+    """The UNI and ZS instances of k_step_tx2 read the X axis' table in all three
+    stages, so the dispatch may take them only where the axes' tables are bitwise
+    equal.  The grids of the catalogue's wide, N8 and ZS entries on ISO_GP with the
+    unequal steps H_GP (whole waves, Z == ZT): the instance with per-axis tables
+    runs, and 3 steps == the oracle, bitwise."""
+    from tests.launch_catalog import _gp, courant_tau
+    b = _gp(2, sizes)
+    random_state(b, seed=sum(sizes), ghosts=False)
+    tau = courant_tau(b)
+    ctx = context_for(b)
+    ctx.profile(True)
+    for step in range(3):
+        for s in range(3):
+            b.stage(s, tau)
+        ctx.step(tau)
+        assert ctx.last_path == "fused"
+        assert_same(ctx, b, f"unequal steps, sizes={sizes} step {step}")
+    k = ctx.profile_read()["fused_xyz"]["kernel"]
+    assert k.startswith(kernel), k
+    ctx.close()
+
+
 @pytest.mark.parametrize("faces", [False, True])
 def test_heterogeneous_step_ode_fused_equals_step_then_ode(G, faces):
     """MaxwellViscosityOde (Ode.hpp:28-37) folded into the heterogeneous one-pass

@@ -32,7 +32,7 @@ EVEN_PADS = {"GCMX_ROW_PAD": "16", "GCMX_PLANE_PAD": "64"}
 # test_odd_strides_take_the_narrow_path shows; the even ones keep the wide path
 PADDED = [("tx2-wide-bs2-4x5x64", "odd"), ("tx2-!uni-bs2-4x6x40", "odd"), ("ortho-bs2-6x9x37", "odd"),
           ("2d-iso-bs2-21x70", "odd"), ("tx2-wide-bs2-4x5x64", "even"), ("acoustic-bs2-4x5x64", "odd"),
-          ("tx2-faces-ode-bs2-4x8x64", "odd")]
+          ("tx2-faces-ode-bs2-4x8x64", "odd"), ("gp-tx2-wide-bs2-4x5x64", "odd")]
 
 
 @pytest.fixture(scope="module")
@@ -118,7 +118,8 @@ def test_padding_with_perturbed_strides(G, monkeypatch, name, pads, fp):
 
 @pytest.mark.parametrize("name", ["tx2-wide-bs2-4x5x64", "tx2-wide-bs1-4x5x64", "tx2-!uni-bs2-4x6x40",
                                   "tx2-zs-bs2-4x12x1024", "ortho-bs2-6x9x37", "2d-iso-bs2-21x70",
-                                  "acoustic-bs2-4x5x64", "tx2-faces-courant15-bs2-4x8x64", "tx2-ode-bs2-4x6x64"])
+                                  "acoustic-bs2-4x5x64", "tx2-faces-courant15-bs2-4x8x64", "tx2-ode-bs2-4x6x64",
+                                  "gp-tx2-wide-bs2-4x5x64"])
 def test_a_value_read_for_a_ghost_is_noticed(G, name):
     """The pair has teeth: the sentinel in ONE element the step does read for a
     ghost (the x ghost next to a central inner node, component 0; the y and z

@@ -15,7 +15,9 @@ ratio where the exact norm is 0).  The scaled states give the contracted kernels
 an exact check of their own: scaling by a power of two commutes with every
 rounding of a fused multiply-add while nothing overflows or underflows, so the
 result from scaled(+-1000) must be ldexp of the same build's unscaled result,
-bit for bit, with no oracle involved.  scaled(-1060) lives among the subnormals,
+bit for bit, with no oracle involved (a value that 2^-1000 takes below the
+normal range -- the contracted residual of a sum that cancels exactly -- is held
+to a few subnormal spacings).  scaled(-1060) lives among the subnormals,
 where that no longer holds: finite, and in the exact build equal to the oracle."""
 import numpy as np
 import pytest
@@ -27,6 +29,8 @@ pytestmark = pytest.mark.gpu
 
 STEPS = 2
 TOL = 1e-10
+TINY = float(np.finfo(np.float64).tiny)
+SUBNORMAL_SLACK = float(np.ldexp(1.0, -1074 + 12))  # test_scaled_states: where the scaled result underflows
 PLACEMENTS = ("centre", "first", "last", "z63", "z64", "z509", "z511", "z512", "z514")
 FAMILIES = tuple(f"impulse-{p}" for p in PLACEMENTS) + ("steps", "steps-zcut", "ramp")
 
@@ -93,9 +97,10 @@ def assert_fma_close(fma, exact, what):
     assert np.isfinite(fma).all(), f"{what}: {int((~np.isfinite(fma)).sum())} non-finite values"
     norm = float(np.linalg.norm(exact))
     if norm == 0.0 or not np.isfinite(norm):
-        return
+        return 0.0
     r = float(np.linalg.norm(fma - exact)) / norm
     assert r <= TOL, f"{what}: FMA against exact, relative L2 {r:.3e} > {TOL}"
+    return r
 
 
 def assert_same_support(got, want, what):
@@ -122,7 +127,7 @@ def test_structured_state(G, entry, family):
     node, bs = fill(entry.body(), family), entry.body().bs
     exact, _ = run_gpu(entry, lambda b: fill(b, family), G.FP_EXACT)
     fma, _ = run_gpu(entry, lambda b: fill(b, family), G.FP_FMA)
-    signs = 0
+    signs, worst = 0, 0.0
     for k, (e, f, w) in enumerate(zip(exact, fma, want)):
         what = f"{entry.name} {family} state {k}"
         signs += assert_canonical(e, w, what)
@@ -130,15 +135,16 @@ def test_structured_state(G, entry, family):
             assert_same_support(e, w, what)
             assert_within_reach(f, entry.node_of(entry.body(), node), bs * (1 + k // (len(want) // STEPS)),
                                 what + " (FMA)")
-        assert_fma_close(f, e, what)
+        worst = max(worst, assert_fma_close(f, e, what))
     print(f"SIGNED-ZEROS {entry.name} {family}: {signs}")
+    print(f"FMA-RATIO {entry.name} {family}: {worst:.3e}")
 
 
 @pytest.mark.parametrize("entry", CATALOG, ids=repr)
 def test_scaled_states(G, entry):
     want = {e: run_oracle(entry, lambda b: states.scaled(b, e)) for e in states.SCALES}
     base = {fp: run_gpu(entry, states.uniform, fp)[0] for fp in (G.FP_EXACT, G.FP_FMA)}
-    signs = 0
+    signs, worst = 0, 0.0
     for e in states.SCALES:
         exact, _ = run_gpu(entry, lambda b: states.scaled(b, e), G.FP_EXACT)
         fma, _ = run_gpu(entry, lambda b: states.scaled(b, e), G.FP_FMA)
@@ -148,12 +154,26 @@ def test_scaled_states(G, entry):
             assert np.isfinite(f).all(), f"{what}: FMA build, {int((~np.isfinite(f)).sum())} non-finite values"
             if e == -1060:
                 continue
-            assert_fma_close(np.ldexp(f, -e), np.ldexp(x, -e), what)  # norms taken near 1
+            worst = max(worst, assert_fma_close(np.ldexp(f, -e), np.ldexp(x, -e), what))  # norms taken near 1
             for name, got, fp in (("exact", x, G.FP_EXACT), ("FMA", f, G.FP_FMA)):
                 ref = np.ldexp(base[fp][k], e)
-                if not np.array_equal(got.view(np.uint64), ref.view(np.uint64)):
-                    diff = got.view(np.uint64) != ref.view(np.uint64)
+                diff = got.view(np.uint64) != ref.view(np.uint64)
+                # the identity's own condition: nothing underflows.  Where a sum cancels
+                # exactly (a free surface's normal stress) the contracted build leaves a
+                # residual of ~1e-17, which 2^-1000 takes among the subnormals: the scaled
+                # run's roundings there are to multiples of 2^-1074, at most 2^-1075 off
+                # each, in fewer than 2^9 operations per value over the three stages
+                # (nine U1 terms of three U terms of an interpolant of <= 8 operations),
+                # amplified by less than 2^3 on the way (|u|, |u1| <= 2.5, each sum a
+                # stable scheme's).  So a subnormal value is held to 2^12 spacings, 2^-50
+                # of the smallest normal number; every normal one and every zero bitwise.
+                underflowed = (ref != 0.0) & (np.abs(ref) < TINY)
+                diff &= ~(underflowed & (np.abs(got - ref) <= SUBNORMAL_SLACK))
+                if diff.any():
                     i0 = tuple(int(v) for v in np.argwhere(diff)[0])
                     raise AssertionError(f"{what}: {name} build, {int(diff.sum())} values are not ldexp of the "
                                          f"unscaled result; first at {i0}: got {got[i0]!r} want {ref[i0]!r}")
+                if underflowed.any():
+                    print(f"UNDERFLOWED {entry.name} scaled({e}) state {k} {name}: {int(underflowed.sum())} values")
     print(f"SIGNED-ZEROS {entry.name} scaled: {signs}")
+    print(f"FMA-RATIO {entry.name} scaled: {worst:.3e}")
